@@ -2,7 +2,7 @@
 # The one GPU-box runner.  gpurun -- 'bash scripts/gpu.sh <tag> <task> [<task> ...]'; output under gpurun_out/<tag>/.
 # A task is name[:arg[:arg...]] (no spaces):
 #   tests[:pytest -k expr]   pytest -m gpu                      smoke                __graft_entry__.smoke()
-#   bench[:cfg[:steps]]      bench.py --config cfg              torchrun             the headline under torch.distributed.run, 1 rank
+#   bench[:cfg[:steps]]      bench.py --config cfg --full       torchrun             the headline under torch.distributed.run, 1 rank
 #   profile[:passes[:sha]]   kernel-trace + 3 PMC runs of scripts/profile_pass.py -> summary.md / summary.json
 #   trace:<script>[:args..]  rocprofv3 --kernel-trace --stats of `python3 scripts/<script> args` -> top kernels
 #   pmc:<kernel>:<ctrs,>:<script>[:args..]   PMC counters of one kernel
@@ -34,7 +34,7 @@ for task in "$@"; do
       echo "pytest rc=$?"; tail -5 $O/pytest.log;;
     smoke) timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2;;
     bench)
-      c=${a1:-headline}; timeout 900 python bench.py --config $c --steps ${a2:-20} --warmup 5 > $O/bench_${c}_n1.json 2> $O/bench_${c}_n1.err
+      c=${a1:-headline}; timeout 900 python bench.py --config $c --steps ${a2:-20} --warmup 5 --full > $O/bench_${c}_n1.json 2> $O/bench_${c}_n1.err
       echo "bench $c rc=$?"; cut -c1-420 $O/bench_${c}_n1.json; tail -2 $O/bench_${c}_n1.err;;
     torchrun)
       timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_headline_torchrun_n1.json 2> $O/bench_headline_torchrun_n1.err

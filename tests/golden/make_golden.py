@@ -20,7 +20,12 @@ import types
 from types import SimpleNamespace
 
 import numpy as np
-import torch
+
+# MKL (torch's CPU exp / sin / cos) rounds fp32 differently per CPU vendor; its reproducible mode gives the same bits on every x86
+# host.  It is fixed when MKL starts, so it is set before torch is imported (tests/test_oracle_golden.py::test_timestep_sinusoid
+# evaluates the oracle in the same mode).
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))

@@ -29,9 +29,23 @@ def test_weight_generator_is_stable():
     assert syn.state_dict_sha256(syn.vae_weights(251)) == want["vae251_seed1235"]
 
 
-def test_timestep_sinusoid():
+def test_timestep_sinusoid(tmp_path):
+    """MKL (torch's CPU exp / sin / cos) rounds fp32 differently per CPU vendor, and at t = 981 one ulp of exp moves sin by 3e-5.
+    The golden is captured in MKL's reproducible mode (make_golden.py), so the oracle is evaluated in that mode too: in a child
+    process, as the mode is fixed when MKL starts."""
+    import subprocess
+    import sys
+    import numpy as np
     g = load_golden("timestep_embedding")
-    assert maxdiff(orc.timestep_sinusoid(g["t"]), g["out"]) < 1e-6
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys, numpy as np, torch; sys.path.insert(0, sys.argv[1]); from oracle import ladiff_oracle as orc; "
+            "np.save(sys.argv[2], orc.timestep_sinusoid(torch.from_numpy(np.load(sys.argv[3]))).numpy())")
+    np.save(tmp_path / "t.npy", g["t"].numpy())
+    env = dict(os.environ, MKL_CBWR="COMPATIBLE")
+    r = subprocess.run([sys.executable, "-c", code, root, str(tmp_path / "out.npy"), str(tmp_path / "t.npy")], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert maxdiff(torch.from_numpy(np.load(tmp_path / "out.npy")), g["out"]) < 1e-6
 
 
 def test_cross_attention_general_n(den_sd):
