@@ -120,10 +120,25 @@ LADIFF_API int ladiff_gemm_split(const float* A, int lda, const float* A2, int l
 
 /* f16x3 operand format ("S-format"): a row of K fp32 values (K multiple of 64) is stored in the same K*4 bytes as
  * K/64 blocks of [64 x 16-bit hi | 64 x 16-bit lo], x ~ hi + lo (fp16 halves, or bf16 in a -DLADIFF_SPLIT_BF16 build).  With split = 1 ladiff_gemm_resident reads A, A2 and W in
- * this format and evaluates every product as hi*hi + hi*lo + lo*hi on the 16-bit MFMA with fp32 accumulation
- * (~2^-16 relative error per product, fp32 exponent range); Ys (may be NULL) receives the K == 256 result in
- * S-format, Y (may then be NULL) in fp32.  ladiff_split_rows converts fp32 [R,K] -> S-format [R,K]. */
+ * this format and evaluates every product as hi*hi + hi*lo + lo*hi on the 16-bit MFMA with fp32 accumulation.
+ * fp16 halves (the default build, both rounded toward zero): |x| in [2^-3, 65504] keeps 22 significant bits (~2^-21 relative
+ * error per operand); below 2^-3 lo reaches fp16's subnormal floor (absolute error up to ~2^-24); each half saturates at +-65504,
+ * so up to 131008 the loss grows gradually and beyond that the value is clipped.  bf16 halves: 16 bits, fp32's exponent range.
+ * Ys (may be NULL) receives the K == 256 result in S-format, Y (may then be NULL) in fp32.  ladiff_split_rows converts fp32 [R,K]
+ * -> S-format [R,K]. */
 LADIFF_API int ladiff_split_rows(const float* x, float* y, int R, int K, ladiff_stream_t stream);
+
+/* What the S-format conversion of this build (ladiff_split_rows) does to n fp32 tensors, one launch: `tensors` [n] and `counts` [n]
+ * are DEVICE arrays (pointer and element count of each tensor), max_count >= every count (sizes the grid; < 2^32).  stats [n][5]
+ * (device, overwritten) receives per tensor:
+ *   [0] max |x| over the values that are not NaN, as the bits of an fp32 in the low word (+inf when the tensor holds one)
+ *   [1] max |x - (hi + lo)| over the finite values, fp32 bits in the low word
+ *   [2] number of non-finite values (NaN, +-inf)
+ *   [3] number of finite values beyond the format's exact range (|x| > 65504 for fp16 halves; always 0 for bf16 halves)
+ *   [4] number of finite non-zero values whose round trip is worse than a single fp16: |x - (hi + lo)| > 2^-11 |x|
+ * Asynchronous on `stream`, no allocation; n == 0 does nothing. */
+LADIFF_API int ladiff_split_range_stats(const float* const* tensors, const int64_t* counts, int n, int64_t max_count,
+                                        uint64_t* stats, ladiff_stream_t stream);
 
 /* The decoder layer's feed-forward block as ONE kernel, f16x3 arithmetic (csrc/dec_mlp.hip):
  *   y / ys [M,256] = LN( x + W2 gelu(W1 x + b1) + b2 ), then a second LayerNorm when ln2_gamma != NULL

@@ -9,6 +9,7 @@ import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_size_t, c_uint64, c_void_p
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -58,6 +59,7 @@ _SIGNATURES = {
     "ladiff_mlp_ln_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, c_void_p]),
     "ladiff_split_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "ladiff_split_range_stats": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]),
     "ladiff_combine_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ladiff_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -242,18 +244,23 @@ class WeightTable:
         self.key = tuple((tensors[n].data_ptr(), tensors[n]._version) for n in names)
         self._split = None
 
+    def _operands(self):
+        """(name, tensor as the S-format table holds it (padded), converted to S-format?) for every tensor of the table."""
+        for n, t in zip(self.names, self.tensors):
+            mult = self.pad_rows.get(n)
+            if mult and t.shape[0] % mult:
+                padded = torch.zeros(((t.shape[0] + mult - 1) // mult * mult,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+                padded[:t.shape[0]] = t
+                t = padded
+            yield n, t, t.dim() == 2 and t.shape[1] % 64 == 0 and n not in self.no_split
+
     def split_array(self):
         """Second pointer table for the f16x3 path: S-format copies of the weight matrices (built once, on the GPU)."""
         if self._split is None:
             L = lib()
             self.split_tensors = []
-            for n, t in zip(self.names, self.tensors):
-                mult = self.pad_rows.get(n)
-                if mult and t.shape[0] % mult:
-                    padded = torch.zeros(((t.shape[0] + mult - 1) // mult * mult,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-                    padded[:t.shape[0]] = t
-                    t = padded
-                if t.dim() == 2 and t.shape[1] % 64 == 0 and n not in self.no_split:
+            for n, t, split in self._operands():
+                if split:
                     s = torch.empty_like(t)
                     check(L.ladiff_split_rows(t.data_ptr(), s.data_ptr(), t.shape[0], t.shape[1], stream_ptr()))
                 else:
@@ -262,9 +269,46 @@ class WeightTable:
             self._split = (c_void_p * self.n_total)(*[t.data_ptr() for t in self.split_tensors])
         return self._split
 
+    def range_report(self):
+        """{name: split_range_stats(...) entry} for exactly the tensors `split_array()` converts to S-format: what the build's split
+        conversion does to them (one launch; waits for the result)."""
+        ops = [(n, t) for n, t, split in self._operands() if split]
+        return dict(zip([n for n, _ in ops], split_range_stats([t for _, t in ops])))
+
     @staticmethod
     def key_of(kind_names, tensors):
         return tuple((tensors[n].data_ptr(), tensors[n]._version) for n in kind_names)
+
+
+SPLIT_RANGE_FIELDS = ("max_abs", "max_err", "nonfinite", "beyond_range", "coarse")
+
+
+def split_range_stats(tensors):
+    """What the loaded build's S-format conversion does to each of a list of fp32 GPU tensors (`ladiff_split_range_stats`, one
+    launch): a list of {"numel", "max_abs", "max_err", "nonfinite", "beyond_range", "coarse"} - max |x| (NaN ignored), max
+    |x - (hi + lo)| over the finite values, and the exact counts of non-finite values, of finite values beyond the format's exact range
+    (|x| > 65504 for fp16 halves, none for bf16 halves) and of non-zero values whose round trip is worse than 2^-11 |x|.
+    Synchronises with the current stream to read the result."""
+    if not tensors:
+        return []
+    dev = tensors[0].device
+    flat = []
+    for t in tensors:
+        ptr(t)                                                  # GPU, fp32, contiguous - or LadiffHipError
+        if t.device != dev:
+            raise LadiffHipError("split_range_stats: all tensors must be on one device")
+        flat.append(t if t.data_ptr() % 16 == 0 else t.clone())  # 16-byte loads (an unaligned tensor would take the scalar pass)
+    counts = [t.numel() for t in flat]
+    with torch.cuda.device(dev):
+        table = torch.tensor([t.data_ptr() for t in flat] + counts, dtype=torch.int64).to(dev)
+        stats = torch.empty(len(flat), 5, dtype=torch.int64, device=dev)
+        check(lib().ladiff_split_range_stats(table.data_ptr(), table.data_ptr() + 8 * len(flat), len(flat), max(counts),
+                                             stats.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        host = stats.cpu().numpy()
+    del flat
+    bits = host[:, :2].astype(np.uint32).view(np.float32)
+    return [{"numel": c, "max_abs": float(bits[i, 0]), "max_err": float(bits[i, 1]), "nonfinite": int(host[i, 2]),
+             "beyond_range": int(host[i, 3]), "coarse": int(host[i, 4])} for i, c in enumerate(counts)]
 
 
 _INT_CACHE = {}

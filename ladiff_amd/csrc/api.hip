@@ -577,6 +577,15 @@ int ladiff_split_rows(const float* x, float* y, int R, int K, ladiff_stream_t st
     return launch_split_rows(x, y, R, K, S(stream));
 }
 
+int ladiff_split_range_stats(const float* const* tensors, const int64_t* counts, int n, int64_t max_count, uint64_t* stats,
+                             ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(n >= 0 && max_count >= 0);
+    if (n == 0) return 0;
+    LADIFF_CHECK_ARG(tensors && counts && stats);
+    if (n > 65535 || max_count >= (int64_t(1) << 32)) return LADIFF_ERR_SHAPE;
+    return launch_split_range_stats(tensors, counts, n, max_count, reinterpret_cast<unsigned long long*>(stats), S(stream));
+}
+
 int ladiff_diffusion_reverse(void* sampler, const float* const* w, const float* const* w_split, uint64_t weights_generation,
                              const float* text_emb, const float* init_noise, const int32_t* counts, const int32_t* final_counts,
                              const int32_t* h_counts, const float* sinusoid, const float* coef, const float* step_noise, float guidance_scale,

@@ -134,6 +134,33 @@ __device__ __forceinline__ float wave_sum(float v) {    // sum over the 64 lanes
     v = dpp_add<0x143, 0xC>(v);    // row_bcast31: rows 2,3 += lane 31
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// the same reduction tree for the maximum of NON-NEGATIVE values (lanes without a source contribute 0) and for unsigned counts
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ float dpp_max(float v) {
+    return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, true)));
+}
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ uint32_t dpp_add_u32(uint32_t v) {
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true);
+}
+__device__ __forceinline__ float wave_max_nonneg(float v) {     // max over the 64 lanes of values >= 0, result in all lanes
+    v = dpp_max<0xB1>(v);
+    v = dpp_max<0x4E>(v);
+    v = dpp_max<0x141>(v);
+    v = dpp_max<0x140>(v);
+    v = dpp_max<0x142, 0xA>(v);
+    v = dpp_max<0x143, 0xC>(v);
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {  // exact integer sum over the 64 lanes, result in all lanes
+    v = dpp_add_u32<0xB1>(v);
+    v = dpp_add_u32<0x4E>(v);
+    v = dpp_add_u32<0x141>(v);
+    v = dpp_add_u32<0x140>(v);
+    v = dpp_add_u32<0x142, 0xA>(v);
+    v = dpp_add_u32<0x143, 0xC>(v);
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
 
 // ---- "split" format (S-format).  A row of K fp32 values occupies the same K*4 bytes as K/64 blocks of
 // [64 x s16 hi | 64 x s16 lo] with x ~ hi + lo.  A product of two split operands is evaluated as hi*hi + hi*lo + lo*hi on the 16-bit
@@ -147,6 +174,10 @@ __device__ __forceinline__ float wave_sum(float v) {    // sum over the 64 lanes
 //     stated in DESIGN.md 1; every product input of these networks is a LayerNorm output, an activation of one, a softmax
 //     probability or a latent.  Same rate, same instruction count as the bf16 form (one v_cvt_pkrtz per two values where the bf16
 //     form needs one v_cvt_pk_bf16 per value).
+//     Ranges of an fp16 pair, both halves rounded toward zero: for |x| in [2^-3, 65504] the pair keeps 22 bits (|x - (hi + lo)| <=
+//     2^-20 |x|); below 2^-3 lo reaches fp16's subnormal floor and the absolute error is up to ~2^-24 (2^-24 is lo's spacing there);
+//     each half saturates at +-65504, so up to 131008 the loss grows gradually and beyond that the value is silently clipped.
+//     ladiff_split_range_stats measures a tensor against exactly these ranges with this conversion (rowops.hip).
 //   * bf16 (-DLADIFF_SPLIT_BF16, rounds 1 - 5, "bf16x3"): 16 significant bits, fp32's exponent range; 2e-4 on the decoded frames of the
 //     50-step benchmark where fp16 pairs give 3e-5.
 #ifndef LADIFF_SPLIT_BF16

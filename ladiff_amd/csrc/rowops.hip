@@ -1,4 +1,6 @@
 // Row-wise / elementwise kernels (HBM- or latency-bound; one wave per 256-float row, 16-byte accesses).
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace ladiff {
@@ -276,6 +278,79 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict
 int launch_split_rows(const float* x, float* y, int R, int K, hipStream_t s) {
     const size_t n4 = (size_t)R * K / 4;
     hipLaunchKernelGGL(split_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, x, y, K, n4);
+    LADIFF_LAUNCH_CHECK();
+    return 0;
+}
+
+// What split_rows_kernel's conversion does to a batch of fp32 tensors (ladiff_split_range_stats).  grid.y = tensor; every block
+// strides over its tensor with 16-byte loads (scalar tail, or a scalar pass when the tensor is not 16-byte aligned), converts with
+// split4 / split2 - the conversion of store_split4 - and adds its waves' results to the tensor's 5 words with global atomics:
+// max |x| and max |x - (hi + lo)| as the bits of non-negative floats (ordered as unsigned integers), then three exact counts.
+#ifndef LADIFF_SPLIT_BF16
+constexpr float SPLIT_EXACT_MAX = 65504.f;          // each fp16 half saturates here
+#else
+constexpr float SPLIT_EXACT_MAX = 3.402823466e38f;  // bf16 halves: fp32's range, no finite value is beyond
+#endif
+
+struct SplitRangeAcc {
+    float max_abs = 0.f, max_err = 0.f;
+    uint32_t nonfinite = 0, beyond = 0, coarse = 0;
+    __device__ __forceinline__ void add(float x, float hi, float lo) {
+        const float ax = fabsf(x);
+        if (!(ax <= 3.402823466e38f)) {               // NaN or +-inf: counted; an infinity is the maximum, a NaN is not ordered
+            ++nonfinite;
+            if (ax == __builtin_huge_valf()) max_abs = ax;
+            return;
+        }
+        max_abs = fmaxf(max_abs, ax);
+        if (ax > SPLIT_EXACT_MAX) ++beyond;
+        const float err = fabsf((x - hi) - lo);
+        max_err = fmaxf(max_err, err);
+        if (ax != 0.f && err > ax * 0x1p-11f) ++coarse;   // worse than a single fp16 (11 significant bits)
+    }
+};
+
+__global__ __launch_bounds__(256) void split_range_stats_kernel(const float* const* __restrict__ xs, const int64_t* __restrict__ counts,
+                                                                unsigned long long* __restrict__ stats) {
+    const int t = blockIdx.y;
+    const int64_t c = counts[t];
+    if (c <= 0) return;
+    const float* __restrict__ x = xs[t];
+    const size_t n = (size_t)c, stride = (size_t)gridDim.x * 256;
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n4 = (reinterpret_cast<uintptr_t>(x) & 15) == 0 ? n / 4 : 0;
+    SplitRangeAcc a;
+    for (size_t i = tid; i < n4; i += stride) {
+        const f32x4 v = ld4(x + i * 4);
+        s16x4 hi, lo;
+        split4(v, hi, lo);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a.add(v[j], (float)hi[j], (float)lo[j]);
+    }
+    for (size_t i = n4 * 4 + tid; i < n; i += stride) {
+        const float v = x[i];
+        s16x2 hi, lo;
+        split2(v, 0.f, hi, lo);
+        a.add(v, (float)hi[0], (float)lo[0]);
+    }
+    const float m = wave_max_nonneg(a.max_abs), e = wave_max_nonneg(a.max_err);
+    const uint32_t nf = wave_sum_u32(a.nonfinite), nb = wave_sum_u32(a.beyond), nc = wave_sum_u32(a.coarse);
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* o = stats + (size_t)t * 5;
+        if (m > 0.f) atomicMax(o + 0, (unsigned long long)__float_as_uint(m));
+        if (e > 0.f) atomicMax(o + 1, (unsigned long long)__float_as_uint(e));
+        if (nf) atomicAdd(o + 2, (unsigned long long)nf);
+        if (nb) atomicAdd(o + 3, (unsigned long long)nb);
+        if (nc) atomicAdd(o + 4, (unsigned long long)nc);
+    }
+}
+int launch_split_range_stats(const float* const* xs, const int64_t* counts, int n, int64_t max_count, unsigned long long* stats,
+                             hipStream_t s) {
+    LADIFF_HIP(hipMemsetAsync(stats, 0, (size_t)n * 5 * sizeof(unsigned long long), s));
+    // ~8 float4 per thread per pass; at most 1024 blocks per tensor (the rest strides)
+    const int64_t per_block = 256 * 4 * 8;
+    const unsigned bx = (unsigned)std::min<int64_t>(1024, std::max<int64_t>(1, (max_count + per_block - 1) / per_block));
+    hipLaunchKernelGGL(split_range_stats_kernel, dim3(bx, (unsigned)n), dim3(256), 0, s, xs, counts, stats);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }

@@ -13,8 +13,10 @@ Out of scope (not built): training/eval steps, metrics, losses, the CLIP text en
 """
 import importlib
 import math
+import os
 import time
 import ctypes
+from collections import OrderedDict
 from ctypes import c_void_p, byref
 
 import numpy as np
@@ -133,6 +135,90 @@ class LADIFF(nn.Module):
         # per-layer buffers of more than ~170 blocks fall out of the 256 MiB memory-side cache (512 prompts in one launch cost 11.5 ms
         # per 128 against 9.8 ms at 256).  None = never split.
         self.max_prompts_per_launch = max_prompts_per_launch
+        # set by LADIFF.load_state_dict (a checkpoint): the next split-mode call checks the split operands' range first
+        self._range_check_pending = False
+        self.t2m_unit_len = int(_cfg_get(_cfg_get(_cfg_get(cfg, "DATASET"), "HUMANML3D"), "UNIT_LEN", 4))
+        if (_cfg_get(model, "condition", "text") in ("text", "text_uncond") and _cfg_get(model, "t2m_textencoder") is not None
+                and _cfg_get(model, "t2m_motionencoder") is not None):
+            self._build_t2m_evaluators(cfg)
+
+    def _build_t2m_evaluators(self, cfg):
+        """The three T2M evaluator networks as children (`_get_t2m_evaluator`, ladiff.py:179-223), so that a checkpoint's `t2m_*` keys
+        load.  Their weights come from `t2m_path/<dataset>/text_mot_match/model/finest.tar` when that file exists, otherwise from the
+        checkpoint loaded afterwards (the reference requires the file).  Host tensors only: nothing here touches the GPU."""
+        from .evaluators import MotionEncoderBiGRUCo, MovementConvEncoder, TextEncoderBiGRUCo
+        model = _cfg_get(cfg, "model")
+        te, me = _cfg_get(model, "t2m_textencoder"), _cfg_get(model, "t2m_motionencoder")
+        nfeats = _cfg_get(_cfg_get(cfg, "DATASET"), "NFEATS", None)
+        nfeats = int(nfeats) if nfeats is not None else int(self.vae.nfeats)
+        self.t2m_textencoder = TextEncoderBiGRUCo(word_size=_cfg_get(te, "dim_word"), pos_size=_cfg_get(te, "dim_pos_ohot"),
+                                                  hidden_size=_cfg_get(te, "dim_text_hidden"), output_size=_cfg_get(te, "dim_coemb_hidden"))
+        self.t2m_moveencoder = MovementConvEncoder(input_size=nfeats - 4, hidden_size=_cfg_get(me, "dim_move_hidden"),
+                                                   output_size=_cfg_get(me, "dim_move_latent"))
+        self.t2m_motionencoder = MotionEncoderBiGRUCo(input_size=_cfg_get(me, "dim_move_latent"), hidden_size=_cfg_get(me, "dim_motion_hidden"),
+                                                      output_size=_cfg_get(me, "dim_motion_latent"))
+        t2m_path = _cfg_get(model, "t2m_path")
+        datasets = _cfg_get(_cfg_get(cfg, "TEST"), "DATASETS")
+        if t2m_path is not None and datasets:
+            dataname = "t2m" if datasets[0] == "humanml3d" else datasets[0]
+            path = os.path.join(t2m_path, dataname, "text_mot_match/model/finest.tar")
+            if os.path.exists(path):
+                ckpt = torch.load(path, map_location="cpu")
+                self.t2m_textencoder.load_state_dict(ckpt["text_encoder"])
+                self.t2m_moveencoder.load_state_dict(ckpt["movement_encoder"])
+                self.t2m_motionencoder.load_state_dict(ckpt["motion_encoder"])
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        """`BaseModel.load_state_dict` (base.py:117-127): incoming `text_encoder.*` keys are dropped and the module's own text-encoder
+        weights are put in their place (checkpoints are saved without CLIP, base.py:96-104), then `nn.Module.load_state_dict` with the
+        caller's `strict`.  A LADiff Lightning checkpoint's `state_dict` holds `denoiser.*`, `vae.*` and `t2m_*`.
+        Marks the model: its next split-mode call checks the range of the split operands first (`check_split_range`)."""
+        own = self.text_encoder.state_dict() if isinstance(self.text_encoder, nn.Module) else {}
+        merged = OrderedDict(("text_encoder." + k, v) for k, v in own.items())
+        merged.update((k, v) for k, v in state_dict.items() if not k.startswith("text_encoder."))
+        if getattr(state_dict, "_metadata", None) is not None:
+            merged._metadata = state_dict._metadata
+        result = super().load_state_dict(merged, strict, **kwargs)
+        self._range_check_pending = True
+        return result
+
+    def check_split_range(self):
+        """Range statistics (`_lib.split_range_stats`) of every tensor the split arithmetic converts to fp16 / bf16 pairs: the denoiser,
+        VAE (decoder and encoder), CLIP text-tower and T2M evaluator tables, on the GPU.  Returns {state-dict key: stats}.  Raises
+        LadiffHipError when, with `precision` in the split mode, an operand that mode converts holds a non-finite value or a value
+        beyond the format's range (fp16 pairs: |x| > 65504) - such a weight would be silently clipped.  The evaluators always run in
+        fp32: their tables are reported, never refused."""
+        tables = [("denoiser.", self.denoiser._weight_table(), True),
+                  ("vae.", self.vae._weight_table(), True),
+                  ("vae.", self.vae._weight_table("encoder"), True)]
+        tower = getattr(self.text_encoder, "text_model", None)
+        if tower is not None and hasattr(tower, "_weight_table"):
+            tables.append(("text_encoder.text_model.", tower._weight_table(), _lib.is_split(getattr(self.text_encoder, "precision", "fp32"))))
+        for name in ("t2m_textencoder", "t2m_moveencoder", "t2m_motionencoder"):
+            net = getattr(self, name, None)
+            if isinstance(net, nn.Module) and hasattr(net, "_weight_table"):
+                tables.append((name + ".", net._weight_table(), False))
+        report, bad = {}, []
+        split = _lib.is_split(self.precision)
+        for prefix, table, runs_split in tables:
+            for key, st in table.range_report().items():
+                report[prefix + key] = st
+                if split and runs_split and (st["nonfinite"] or st["beyond_range"]):
+                    bad.append((prefix + key, st))
+        if bad:
+            key, st = bad[0]
+            raise _lib.LadiffHipError(
+                f"weight {key} cannot be split into {_lib.split_mode_name()} pairs: {st['nonfinite']} non-finite value(s), "
+                f"{st['beyond_range']} beyond the format's range (max |x| = {st['max_abs']:.6g})"
+                + (f"; {len(bad) - 1} more weight(s) affected" if len(bad) > 1 else "")
+                + '.  Call ladiff_amd._lib.select_split_format("bf16") before first use (fp32 exponent range) or use precision="fp32"')
+        return report
+
+    def _check_loaded_weights(self):
+        """Once after LADIFF.load_state_dict, at the first split-mode call and before anything of it is launched."""
+        if self._range_check_pending and _lib.is_split(self.precision):
+            self.check_split_range()
+            self._range_check_pending = False
 
     # ------------------------------------------------------------------ plumbing
     @property
@@ -285,6 +371,7 @@ class LADIFF(nn.Module):
         dev = encoder_hidden_states.device
         if not encoder_hidden_states.is_cuda:
             raise _lib.LadiffHipError("_diffusion_reverse needs GPU tensors; there is no CPU fallback")
+        self._check_loaded_weights()
         # earlier calls' status: the last-but-one call's words are waited for (long there), the previous call's only if they have
         # arrived - the host never blocks on a loop that is still running, and no status is dropped unread
         self._call += 1
@@ -481,6 +568,7 @@ class LADIFF(nn.Module):
         if self.text_encoder is None or (self.feats2joints is None and self.feats2joints_device is None):
             raise RuntimeError("LADIFF.forward needs a text_encoder callable and datamodule.feats2joints; "
                                "use .sample(text_emb, lengths) for embeddings -> features")
+        self._check_loaded_weights()
         start = time.time()
         text_emb = self.text_encoder(self._guided_texts(texts))
         z = self._diffusion_reverse(text_emb, lengths)
@@ -517,6 +605,7 @@ class LADIFF(nn.Module):
         reference's `rs_set`: m_rst [B,F,C], lat_t [B,max_it,256], joints_rst, (m_ref, lat_m, lat_rm, joints_ref)."""
         if self.text_encoder is None or (self.feats2joints is None and self.feats2joints_device is None):
             raise RuntimeError("test_diffusion_forward needs a text_encoder callable and datamodule.feats2joints")
+        self._check_loaded_weights()
         lengths = [int(l) for l in batch["length"]]
         cond_emb = self.text_encoder(self._guided_texts(batch["text"]))                  # :1038-1048
         f2j = self.feats2joints_device or (lambda f: self.feats2joints(f.detach().cpu()))
@@ -538,7 +627,10 @@ class LADIFF(nn.Module):
     def set_t2m_evaluators(self, text_encoder, movement_encoder, motion_encoder, unit_len=4):
         """The three frozen evaluator networks of `_get_t2m_evaluator` (ladiff.py:179-223); `unit_len` =
         cfg.DATASET.HUMANML3D.UNIT_LEN (ladiff.py:1259-1261)."""
-        self.t2m_textencoder, self.t2m_moveencoder, self.t2m_motionencoder = text_encoder, movement_encoder, motion_encoder
+        for name, net in (("t2m_textencoder", text_encoder), ("t2m_moveencoder", movement_encoder), ("t2m_motionencoder", motion_encoder)):
+            if name in self._modules and not isinstance(net, nn.Module):
+                del self._modules[name]                # a plain callable replaces the child built from the config
+            setattr(self, name, net)
         self.t2m_unit_len = int(unit_len)
 
     def t2m_eval(self, batch):
@@ -548,6 +640,7 @@ class LADIFF(nn.Module):
             raise RuntimeError("call set_t2m_evaluators(text_encoder, movement_encoder, motion_encoder) first")
         if self.text_encoder is None or not hasattr(self.datamodule, "renorm4t2m"):
             raise RuntimeError("t2m_eval needs a text_encoder and datamodule.renorm4t2m / feats2joints")
+        self._check_loaded_weights()
         texts, lengths = list(batch["text"]), [int(l) for l in batch["length"]]
         dev = self.device
         motions = batch["motion"].detach().clone().to(dev)
@@ -576,12 +669,14 @@ class LADIFF(nn.Module):
     def recon_from_motion(self, batch):
         """encode -> decode -> joints of the reconstruction and of the input (ladiff.py:320-331)."""
         feats_ref, length = batch["motion"], batch["length"]
+        self._check_loaded_weights()
         z, dist, _ = self.vae.encode(feats_ref, length)
         feats_rst = self.vae.decode(z, length)
         f2j = self.feats2joints_device or (lambda f: self.feats2joints(f.detach().cpu()))
         return remove_padding(f2j(feats_rst.detach()).cpu(), length), remove_padding(f2j(feats_ref.detach()).cpu(), length)
 
     def gen_from_latent(self, batch):
+        self._check_loaded_weights()
         feats_rst = self.vae.decode(batch["latent"], batch["length"])
         if self.feats2joints_device is not None:
             return remove_padding(self.feats2joints_device(feats_rst.detach()).cpu(), batch["length"])
