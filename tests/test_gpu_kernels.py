@@ -7,6 +7,7 @@ import torch.nn.functional as F
 
 from ladiff_amd import _lib
 from oracle import ladiff_oracle as orc
+from trained_like import layernorm_row_bound, offset_rows, spread_affine
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -220,7 +221,42 @@ def from_split(y):
     return (b[:, :, 0] + b[:, :, 1]).reshape(y.shape[0], y.shape[1])
 
 
-def gemm_resident(A, W, bias=None, A2=None, res=None, act="none", split=False, want_split_out=False):
+def split_planes(y):
+    """S-format [R,K] (GPU) -> (hi, lo) in fp64 on the CPU, decoded separately: the very values the kernel's MFMAs read."""
+    half = torch.float16 if lib().ladiff_split_format() == 1 else torch.bfloat16
+    b = y.cpu().contiguous().view(half).view(y.shape[0], y.shape[1] // 64, 2, 64).double()
+    return b[:, :, 0].reshape(y.shape[0], y.shape[1]), b[:, :, 1].reshape(y.shape[0], y.shape[1])
+
+
+ACTS = {"none": lambda v: v, "relu": F.relu, "gelu": F.gelu, "silu": F.silu, "qgelu": lambda v: v * torch.sigmoid(1.702 * v),
+        "lrelu": lambda v: F.leaky_relu(v, 0.2)}
+
+
+def assert_three_term_product(got, As, Ws, K, bias=None, res=None, act="none", A2s=None):
+    """Per element: the kernel's result against hi*hi + hi*lo + lo*hi of the S-format operands it read, evaluated in fp64.  What is left
+    is fp32 accumulation only: (K + 4) 2^-24 (|A| |W|^T)[i, j] (+ the roundings of bias / residual / output, and the activations'
+    slope <= 1.13).  A kernel that drops one cross term (2^-11 per operand) or reads a lo plane of another k block misses it."""
+    ah, al = split_planes(As)
+    if A2s is not None:
+        ah2, al2 = split_planes(A2s)
+        ah, al = torch.cat([ah, ah2], 1), torch.cat([al, al2], 1)
+    wh, wl = split_planes(Ws)
+    emu = ah @ wh.t() + ah @ wl.t() + al @ wh.t()
+    mag = (ah + al).abs() @ (wh + wl).abs().t()
+    tiny = emu.abs()
+    if bias is not None:
+        emu, tiny = emu + bias.double(), tiny + bias.double().abs()
+    emu = ACTS[act](emu)
+    if res is not None:
+        emu, tiny = emu + res.double(), tiny + res.double().abs()
+    bnd = 1.13 * (K + 4) * 2.0 ** -24 * mag + 4 * 2.0 ** -24 * tiny + 1e-30
+    err = (got.double() - emu).abs()
+    worst = (err / bnd).max().item()
+    print(f"three-term emulation: max err / bound = {worst:.3f} (max err {err.max().item():.3e})")
+    assert (err <= bnd).all(), worst
+
+
+def gemm_resident(A, W, bias=None, A2=None, res=None, act="none", split=False, want_split_out=False, keep=None):
     M, K1 = A.shape
     N, K = W.shape
     splits = K // 256
@@ -229,6 +265,8 @@ def gemm_resident(A, W, bias=None, A2=None, res=None, act="none", split=False, w
     if split:
         A_, W_ = to_split(A_), to_split(W_)
         A2_ = None if A2_ is None else to_split(A2_)
+        if keep is not None:
+            keep.update(A=A_, W=W_, A2=A2_)
     Y = torch.full((splits, M, N) if splits > 1 else (M, N), float("nan"), device=DEV)
     Ys = torch.zeros(M, N, device=DEV) if want_split_out else None
     _lib.check(lib().ladiff_gemm_resident(_lib.ptr(A_), A_.shape[1], _lib.ptr(A2_), 0 if A2 is None else A2_.shape[1], K1,
@@ -261,9 +299,11 @@ def test_split_operands_saturate_instead_of_overflowing():
         assert ((back - x).abs() <= 2.0 ** -16 * x.abs()).all()
     # a product whose operands sit just inside fp16's range: finite, and as accurate as any other
     A, W = rnd(64, 256, scale=15000.0), rnd(256, 256, scale=1 / 16)
-    got = gemm_resident(A, W, split=True)
+    ops = {}
+    got = gemm_resident(A, W, split=True, keep=ops)
     want = ref_gemm(A, W)
     assert torch.isfinite(got).all()
+    assert_three_term_product(got, ops["A"], ops["W"], 256)
     bits = 20 if lib().ladiff_split_format() == 1 else 14
     assert (got.double() - want).abs().max().item() < 2.0 ** -bits * (A.abs().double() @ W.abs().double().t()).max().item()
 
@@ -275,12 +315,18 @@ def test_gemm_resident_split(M, N, K, act):
     A, W, b = rnd(M, K, scale=3.0), rnd(N, K, scale=1 / math.sqrt(K)), rnd(N)
     if K == 256:
         res = rnd(M, N, seed=7)
-        got, got_s = gemm_resident(A, W, b, res=res, act=act, split=True, want_split_out=True)
+        ops = {}
+        got, got_s = gemm_resident(A, W, b, res=res, act=act, split=True, want_split_out=True, keep=ops)
         want = ref_gemm(A, W, b, res=res, act=act)
         assert (got_s.double() - got.double()).abs().max().item() <= 2.0 ** -15 * got.abs().max().item()
+        assert_three_term_product(got, ops["A"], ops["W"], K, b, res, act)
     else:
-        got = gemm_resident(A, W, split=True).double().sum(0)
+        ops = {}
+        planes = gemm_resident(A, W, split=True, keep=ops)
+        got = planes.double().sum(0)
         want = ref_gemm(A, W)
+        for i in range(K // 256):                                  # every K / 256 partial plane by itself
+            assert_three_term_product(planes[i], ops["A"][:, 256 * i:256 * (i + 1)], ops["W"][:, 256 * i:256 * (i + 1)], 256)
     bound = 4 * 2.0 ** -16 * (A.abs().double() @ W.abs().double().t()).max().item()
     assert (got.double() - want).abs().max().item() < bound
 
@@ -357,6 +403,7 @@ def test_gemm_split_large_m(M, N, K, act, concat, res):
     got = Y.cpu()
     bound = 4 * 2.0 ** -16 * (A.abs().double() @ W.abs().double().t()).max().item() + 2e-6
     assert torch.isfinite(got).all() and (got.double() - want).abs().max().item() < bound
+    assert_three_term_product(got, As, Ws, K, b, R, act, A2s)
     assert (from_split(Ys).double() - got.double()).abs().max().item() <= 2.0 ** -15 * got.abs().max().item()
     assert lib().ladiff_gemm_split(_lib.ptr(As), K1, None, 0, K1, _lib.ptr(Ws), K, None, None, 0, _lib.ptr(Y), None, N, M, 100,
                                    K, 0, _lib.stream_ptr()) == -2          # N must be a multiple of 128
@@ -574,3 +621,137 @@ def test_graphed_decode_matches_direct_decode():
                 st.synchronize()
                 assert torch.equal(got2, want), (precision, lens)
     assert len(vae._dec_plans) <= 4
+
+
+# ---------------------------------------------------------------- small and zero operands of the split products
+@pytest.mark.parametrize("kernel", ["resident", "large_m"])
+def test_split_products_of_small_operands_per_element(kernel):
+    """Rows of A below 2^-3 (their lo halves in fp16's subnormal range) and below 2^-14 (hi halves too), a W row (= output column) of exact
+    zeros: per element against the three-term emulation of the S-format operands, and the zero column gives exactly the bias."""
+    M, N, K = 200, 256, 256
+    A, W, b = rnd(M, K), rnd(N, K, scale=1 / 16), rnd(N)
+    A[1::4] *= 2.0 ** -5
+    A[2::4] *= 2.0 ** -16
+    A[3::4] *= 2.0 ** -20
+    W[5] = 0
+    W[6] *= 2.0 ** -15
+    As, Ws = to_split(A), to_split(W)
+    Y = torch.full((M, N), float("nan"), device=DEV)
+    bd = b.to(DEV)
+    if kernel == "resident":
+        _lib.check(lib().ladiff_gemm_resident(_lib.ptr(As), K, None, 0, K, _lib.ptr(Ws), K, _lib.ptr(bd), None, 0, _lib.ptr(Y), N, M, N, K,
+                                              0, 1, None, _lib.stream_ptr()))
+    else:
+        _lib.check(lib().ladiff_gemm_split(_lib.ptr(As), K, None, 0, K, _lib.ptr(Ws), K, _lib.ptr(bd), None, 0, _lib.ptr(Y), None, N, M, N,
+                                           K, 0, _lib.stream_ptr()))
+    sync()
+    got = Y.cpu()
+    assert torch.isfinite(got).all() and torch.equal(got[:, 5], b[5].expand(M))
+    assert_three_term_product(got, As, Ws, K, b)
+    bits = 20 if lib().ladiff_split_format() == 1 else 14
+    # against the true product: the small rows lose their lo halves (fp16 pairs), so the bound is relative to the LARGEST row, as before
+    assert (got.double() - ref_gemm(A, W, b)).abs().max().item() < 2.0 ** -bits * (A.abs().double() @ W.abs().double().t()).max().item()
+
+
+# ---------------------------------------------------------------- LayerNorm on rows a one-pass variance gets wrong
+def assert_layernorm_rows(got, x64, gamma, beta, what, input_err=0.0, post=None, slope=1.0):
+    """fp64 reference, per-row bound of trained_like.layernorm_row_bound (derived, not measured); `post` maps the normalised rows to the
+    kernel's output (slope = its largest derivative)."""
+    want = F.layer_norm(x64, (256,), gamma.double(), beta.double(), 1e-5)
+    if post is not None:
+        want = post(want)
+    bnd = slope * layernorm_row_bound(x64, gamma, input_err)
+    err = (got.double() - want).abs()
+    ratio = (err / bnd).amax(dim=1)
+    print(f"{what}: err / row bound by row kind (mean 1000, mean -300, constant, outlier, plain): " +
+          ", ".join(f"{ratio[k::5].max().item():.3f}" for k in range(min(5, len(ratio)))))
+    assert torch.isfinite(got).all() and (err <= bnd).all(), (what, ratio.max().item())
+
+
+@pytest.mark.parametrize("M", [5, 40, 1285])
+def test_layernorm_offset_rows(M):
+    x = offset_rows(M, seed=M)
+    g, b = spread_affine(3)
+    y = torch.full((M, 256), float("nan"), device=DEV)
+    xd, gd, bd = x.to(DEV), g.to(DEV), b.to(DEV)
+    _lib.check(lib().ladiff_layernorm(_lib.ptr(xd), _lib.ptr(gd), _lib.ptr(bd), _lib.ptr(y), M, _lib.stream_ptr()))
+    sync()
+    assert_layernorm_rows(y.cpu(), x.double(), g, b, f"ladiff_layernorm M={M}")
+
+
+@pytest.mark.parametrize("M,K", [(40, 256), (1285, 256), (4100, 256), (45, 1024)])
+def test_gemm_layernorm_offset_rows(M, K):
+    """`ladiff_gemm` with ln_gamma: the offsets enter through the residual; the product's fp32 accumulation error is part of the bound."""
+    A, W, b = rnd(M, K, scale=0.05), rnd(256, K, scale=1 / math.sqrt(K)), rnd(256, scale=0.1)
+    res = offset_rows(M, seed=M + K)
+    ln = spread_affine(4)
+    got = gemm(A, W, b, res=res, ln=ln)
+    x64 = ref_gemm(A, W, b, res=res)
+    gemm_err = (K + 4) * 2.0 ** -24 * ((A.abs().double() @ W.abs().double().t()) + b.abs().double()).amax(dim=1, keepdim=True)
+    assert_layernorm_rows(got, x64, ln[0], ln[1], f"ladiff_gemm + LayerNorm M={M} K={K}", input_err=gemm_err)
+
+
+@pytest.mark.parametrize("M,planes", [(40, 2), (45, 4), (1285, 2)])
+def test_combine_rows_offset_rows(M, planes):
+    """`ladiff_combine_rows` modes 1 - 3 (LayerNorm, + c-table row, AdaLN modulation + SiLU) on K / 256 partial planes + bias + residual."""
+    P, b = 0.05 * rnd(planes * M, 256).view(planes, M, 256), rnd(256, scale=0.1)
+    res = offset_rows(M, seed=M + planes)
+    g, be = spread_affine(5)
+    T, Bs = 5, 4
+    nsamp = (M + T - 1) // T
+    counts = torch.tensor([5, 2, 3, 1], dtype=torch.int32)
+    ctab, mod = rnd(nsamp + 1, 256, seed=11), rnd(512, seed=12)
+    x64 = P.double().sum(0) + b.double() + res.double()
+    rows = torch.arange(M)
+    valid = (rows % T) < counts[(rows // T) % Bs]
+    sel = torch.where(valid, rows // T, torch.tensor(nsamp))
+    sum_err = (planes + 2) * 2.0 ** -24 * (P.abs().double().sum(0) + b.abs().double()).amax(dim=1, keepdim=True)
+    posts = {1: (None, 1.0), 2: (lambda v: v + ctab.double()[sel], 1.0),
+             3: (lambda v: F.silu(v * (1 + mod[:256].double()) + mod[256:].double()), 1.1 * (1 + mod[:256].abs().max().item()))}
+    pd, bd, rd, gd, bed = P.contiguous().to(DEV), b.to(DEV), res.to(DEV), g.to(DEV), be.to(DEV)
+    for mode, tab in ((1, None), (2, ctab), (3, mod)):
+        out = torch.full((M, 256), float("nan"), device=DEV)
+        td = None if tab is None else tab.to(DEV)
+        _lib.check(lib().ladiff_combine_rows(_lib.ptr(pd), planes, M, _lib.ptr(bd), _lib.ptr(rd), mode, _lib.ptr(gd), _lib.ptr(bed),
+                                             _lib.ptr(td), counts.to(DEV).data_ptr(), Bs, T, nsamp, _lib.ptr(out), _lib.stream_ptr()))
+        sync()
+        post, slope = posts[mode]
+        assert_layernorm_rows(out.cpu(), x64, g, be, f"ladiff_combine_rows mode {mode} M={M} planes={planes}", input_err=sum_err, post=post,
+                              slope=slope)
+
+
+@pytest.mark.parametrize("through", ["x", "b2"])
+@pytest.mark.parametrize("M,second_ln", [(40, False), (45, True), (1285, True)])
+def test_fused_mlp_layernorm_offset_rows(M, second_ln, through):
+    """`ladiff_mlp_ln_fused`, y = LN(x + W2 gelu(W1 x_s + b1) + b2) [then a second LN]: the offsets enter through the fp32 residual rows x
+    (the S-format operand x_s keeps the small values) or through b2 (every row's mean moves by 1000).  The split products' own error
+    (2^-21 per operand with fp16 pairs, 2^-16 with bf16 pairs; two operands per product, two products in the chain, gelu' <= 1.13) is part
+    of the bound, derived from the fp64 operands.  The second LayerNorm sees rows of O(gamma): its bound is the first one's, passed
+    through its own division and gamma."""
+    xs_small = rnd(M, 256, scale=2.0, seed=1)
+    w1, b1 = rnd(1024, 256, scale=1 / 16, seed=2), rnd(1024, scale=0.5, seed=3)
+    w2, b2 = rnd(256, 1024, scale=1 / 32, seed=4), rnd(256, scale=0.5, seed=5)
+    (g3, be3), (g4, be4) = spread_affine(6), spread_affine(8)
+    x = xs_small + offset_rows(M, seed=M) if through == "x" else xs_small
+    if through == "b2":
+        b2 = b2 + 1000.0
+    d = lambda t: t.to(DEV).contiguous()
+    xs, w1s, w2s = split_rows(d(xs_small)), split_rows(d(w1)), split_rows(d(w2))
+    xd, b1d, b2d, g3d, be3d, g4d, be4d = d(x), d(b1), d(b2), d(g3), d(be3), d(g4), d(be4)
+    y = torch.full((M, 256), float("nan"), device=DEV)
+    _lib.check(lib().ladiff_mlp_ln_fused(_lib.ptr(xs), _lib.ptr(xd), _lib.ptr(w1s), _lib.ptr(b1d), _lib.ptr(w2s), _lib.ptr(b2d),
+                                         _lib.ptr(g3d), _lib.ptr(be3d), _lib.ptr(g4d) if second_ln else None,
+                                         _lib.ptr(be4d) if second_ln else None, _lib.ptr(y), None, M, _lib.stream_ptr()))
+    sync()
+    h = F.gelu(F.linear(xs_small.double(), w1.double(), b1.double()))
+    pre = x.double() + F.linear(h, w2.double(), b2.double())
+    u = 2.0 ** (-21 if lib().ladiff_split_format() == 1 else -16)
+    h_err = 1.13 * (2 * u + 260 * 2.0 ** -24) * (xs_small.abs().double() @ w1.abs().double().t())
+    prod_err = ((2 * u + 1028 * 2.0 ** -24) * (h.abs() @ w2.abs().double().t()) + h_err @ w2.abs().double().t()).amax(dim=1, keepdim=True)
+    if not second_ln:
+        assert_layernorm_rows(y.cpu(), pre, g3, be3, f"ladiff_mlp_ln_fused offset through {through} M={M}", input_err=prod_err)
+        return
+    mid = F.layer_norm(pre, (256,), g3.double(), be3.double(), 1e-5)
+    mid_err = layernorm_row_bound(pre, g3, prod_err)                      # what the first LayerNorm may hand to the second
+    assert_layernorm_rows(y.cpu(), mid, g4, be4, f"ladiff_mlp_ln_fused + second LayerNorm, offset through {through} M={M}",
+                          input_err=mid_err)
