@@ -128,6 +128,13 @@ LADIFF_API int ladiff_gemm_split(const float* A, int lda, const float* A2, int l
  * -> S-format [R,K]. */
 LADIFF_API int ladiff_split_rows(const float* x, float* y, int R, int K, ladiff_stream_t stream);
 
+/* dst[r][:] = src[index[r]][:] for r < n_rows: rows of row_floats floats (a multiple of 4; src and dst 16-byte aligned, rows contiguous),
+ * index [n_rows] int32 on the DEVICE.  Pure data movement (bit-exact): expands per-prompt rows to per-sample rows - the R repeats of each
+ * prompt in the multimodality pass (ladiff.py:1122-1132) and the "" rows of the guidance half of a [2B,1,768] text tensor - for callers
+ * without torch.  The entry checks what the host can see (sizes, alignment); the index VALUES are device data: the caller must pass
+ * 0 <= index[r] < rows of src.  src and dst must not overlap.  Asynchronous on `stream`; n_rows == 0 does nothing. */
+LADIFF_API int ladiff_gather_rows(const float* src, const int32_t* index, int n_rows, int row_floats, float* dst, ladiff_stream_t stream);
+
 /* What the S-format conversion of this build (ladiff_split_rows) does to n fp32 tensors, one launch: `tensors` [n] and `counts` [n]
  * are DEVICE arrays (pointer and element count of each tensor), max_count >= every count (sizes the grid; < 2^32).  stats [n][5]
  * (device, overwritten) receives per tensor:

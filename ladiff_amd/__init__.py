@@ -9,7 +9,8 @@ from .pipeline import LADIFF, instantiate_from_config   # noqa: F401
 from .schedulers import DDIMScheduler, DDPMScheduler    # noqa: F401
 from .text_encoder import MldTextEncoder                # noqa: F401
 from .evaluators import (MovementConvEncoder, MotionEncoderBiGRUCo, TextEncoderBiGRUCo,   # noqa: F401
-                         TM2TMetrics)
+                         TM2TMetrics, MMMetrics)
+from .evaluation import evaluate, get_metric_statistics   # noqa: F401
 
 __all__ = ["LADiffDenoiser", "LADiffVae", "LADIFF", "DDIMScheduler", "DDPMScheduler", "instantiate_from_config", "Feats2Joints", "MldTextEncoder", "MovementConvEncoder", "MotionEncoderBiGRUCo", "TextEncoderBiGRUCo",
-           "TM2TMetrics"]
+           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics"]

@@ -60,6 +60,7 @@ _SIGNATURES = {
                                     c_void_p, c_void_p, c_int, c_void_p]),
     "ladiff_split_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ladiff_split_range_stats": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_int64, c_void_p, c_void_p]),
+    "ladiff_gather_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "ladiff_combine_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ladiff_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -309,6 +310,27 @@ def split_range_stats(tensors):
     bits = host[:, :2].astype(np.uint32).view(np.float32)
     return [{"numel": c, "max_abs": float(bits[i, 0]), "max_err": float(bits[i, 1]), "nonfinite": int(host[i, 2]),
              "beyond_range": int(host[i, 3]), "coarse": int(host[i, 4])} for i, c in enumerate(counts)]
+
+
+def gather_rows(src, index):
+    """out[r] = src[index[r]] over the leading dimension of a contiguous fp32 GPU tensor (`ladiff_gather_rows`: data movement, bit-exact).
+    `index` is a HOST sequence of ints: it is range-checked here, against src's row count, before anything is launched."""
+    ptr(src)
+    idx = [int(i) for i in index]
+    if src.dim() < 1 or src.shape[0] == 0 or any(i < 0 or i >= src.shape[0] for i in idx):
+        raise IndexError(f"gather_rows: index out of range for {src.shape[0] if src.dim() else 0} rows")
+    row = src[0].numel()
+    if row % 4:
+        raise LadiffHipError(f"gather_rows: rows of {row} floats are not whole 16-byte chunks")
+    if src.data_ptr() % 16:
+        src = src.clone()
+    out = torch.empty((len(idx),) + tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    if idx:
+        with torch.cuda.device(src.device):
+            d_idx = device_ints(idx, src.device)
+            check(lib().ladiff_gather_rows(src.data_ptr(), d_idx.data_ptr(), len(idx), row, out.data_ptr(),
+                                           torch.cuda.current_stream(src.device).cuda_stream))
+    return out
 
 
 _INT_CACHE = {}

@@ -577,6 +577,16 @@ int ladiff_split_rows(const float* x, float* y, int R, int K, ladiff_stream_t st
     return launch_split_rows(x, y, R, K, S(stream));
 }
 
+int ladiff_gather_rows(const float* src, const int32_t* index, int n_rows, int row_floats, float* dst, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(n_rows >= 0 && row_floats > 0);
+    if (n_rows == 0) return 0;
+    LADIFF_CHECK_ARG(src && index && dst);
+    // what the host can see: 16-byte rows at 16-byte addresses, and a grid that fits (the index VALUES are device data)
+    if (row_floats % 4 || (reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(dst) & 15)) return LADIFF_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(index) & 3) || n_rows > (1 << 30)) return LADIFF_ERR_SHAPE;
+    return launch_gather_rows(src, index, n_rows, row_floats, dst, S(stream));
+}
+
 int ladiff_split_range_stats(const float* const* tensors, const int64_t* counts, int n, int64_t max_count, uint64_t* stats,
                              ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(n >= 0 && max_count >= 0);

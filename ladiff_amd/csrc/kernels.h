@@ -12,6 +12,7 @@ int launch_reduce_rows(const float* P, int S, int M, const float* bias, const fl
                        const int32_t* counts, int Bs, int T, int pad_row, int b_off, float* out, float* outs, hipStream_t s,
                        const int32_t* d_base = nullptr, const float* g2 = nullptr, const float* b2 = nullptr);   // g2 / b2: RED_LN twice
 int launch_split_rows(const float* x, float* y, int R, int K, hipStream_t s);
+int launch_gather_rows(const float* src, const int32_t* index, int n_rows, int row_floats, float* dst, hipStream_t s);
 int launch_split_range_stats(const float* const* xs, const int64_t* counts, int n, int64_t max_count, unsigned long long* stats,
                              hipStream_t s);
 int launch_layernorm(const float* x, const float* g, const float* b, float* y, int M, hipStream_t s);

@@ -267,6 +267,25 @@ int launch_broadcast_pe(const float* pe, int B, int F, float* x, float* xs, hipS
     return 0;
 }
 
+// dst[r, :] = src[index[r], :] for rows of `row_floats` floats (a multiple of 4; both tensors 16-byte aligned): one wave per row, 16-byte
+// loads and stores.  Expands per-prompt rows to per-sample rows (the R repeats of a prompt in the multimodality pass, the "" rows of the
+// guidance half).  The indices live on the device: 0 <= index[r] < rows of src is the caller's to guarantee.
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ index, int n_rows,
+                                                          int row4, float* __restrict__ dst) {
+    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const float* s = src + (size_t)index[row] * row4 * 4;
+    float* d = dst + (size_t)row * row4 * 4;
+    for (int c = threadIdx.x & 63; c < row4; c += 64) st4(d + c * 4, ld4(s + c * 4));
+}
+int launch_gather_rows(const float* src, const int32_t* index, int n_rows, int row_floats, float* dst, hipStream_t s) {
+    if (n_rows == 0) return 0;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((n_rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, src, index, n_rows,
+                       row_floats / 4, dst);
+    LADIFF_LAUNCH_CHECK();
+    return 0;
+}
+
 // fp32 [R][K] -> S-format [R][K] (weights are split once per weight table; K multiple of 64)
 __global__ __launch_bounds__(256) void split_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int K, size_t n4) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

@@ -5,6 +5,7 @@ to turn generated motions into R-precision / FID / matching-score / diversity nu
     ladiff.models.architectures.t2m_motionenc.MotionEncoderBiGRUCo  -> ladiff_amd.evaluators.MotionEncoderBiGRUCo
     ladiff.models.architectures.t2m_textenc.TextEncoderBiGRUCo      -> ladiff_amd.evaluators.TextEncoderBiGRUCo
     ladiff.models.metrics.tm2t.TM2TMetrics                          -> ladiff_amd.evaluators.TM2TMetrics
+    ladiff.models.metrics.mm.MMMetrics                              -> ladiff_amd.evaluators.MMMetrics
 
 The three networks keep the reference's constructor arguments and state-dict keys (the `movement_encoder` /
 `motion_encoder` / `text_encoder` sub-dicts of the evaluator checkpoint load with `strict=True`, `ladiff.py:205-212`) and run
@@ -210,4 +211,41 @@ class TM2TMetrics:
         i2 = self.rng.choice(n, self.diversity_times, replace=False) if div_second is None else np.asarray(div_second)
         out["Diversity"] = float(np.linalg.norm(rec[i1] - rec[i2], axis=1).mean())
         out["gt_Diversity"] = float(np.linalg.norm(gt[i1] - gt[i2], axis=1).mean())
+        return out
+
+
+class MMMetrics:
+    """MultiModality of the multimodality pass (`metrics/mm.py`, `metrics/utils.py:247-261`): for every prompt, the mean distance between
+    `mm_num_times` pairs of the evaluator embeddings of its R generated motions, averaged over the prompts.  `update` caches
+    [prompts, R, 512] batches, `compute` evaluates on the host in fp64.  The reference's two `choice(R, mm_num_times, replace=False)` draws
+    come from `numpy.random.Generator(seed)`, or from the caller (`first`, `second`)."""
+
+    def __init__(self, mm_num_times=10, dist_sync_on_step=True, seed=0, **kwargs):
+        self.name = "MultiModality scores"
+        self.mm_num_times = mm_num_times
+        self.metrics = ["MultiModality"]
+        self.rng = np.random.default_rng(seed)
+        self.reset()
+
+    def reset(self):
+        self.count = 0
+        self.count_seq = 0
+        self._mm = []
+
+    def update(self, mm_motion_embeddings, lengths):
+        self.count += int(sum(lengths))
+        self.count_seq += len(lengths)
+        self._mm.append(torch.as_tensor(mm_motion_embeddings).detach().cpu().double().numpy())
+
+    def compute(self, sanity_flag=False, first=None, second=None):
+        out = {m: 0.0 for m in self.metrics}
+        if sanity_flag:
+            return out
+        act = np.concatenate(self._mm, axis=0)
+        assert act.ndim == 3
+        assert act.shape[1] > self.mm_num_times
+        R = act.shape[1]
+        first = self.rng.choice(R, self.mm_num_times, replace=False) if first is None else np.asarray(first)
+        second = self.rng.choice(R, self.mm_num_times, replace=False) if second is None else np.asarray(second)
+        out["MultiModality"] = float(np.linalg.norm(act[:, first] - act[:, second], axis=2).mean())
         return out

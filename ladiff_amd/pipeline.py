@@ -70,7 +70,7 @@ class LADIFF(nn.Module):
     def __init__(self, cfg=None, datamodule=None, *, denoiser=None, vae=None, scheduler=None, text_encoder=None,
                  guidance_scale=None, num_inference_timesteps=None, eta=None, max_it=None, frame_per_latent=None,
                  test_efficiency=None, use_graph=True, precision=None, loop="pipeline", fallback=False,
-                 max_prompts_per_launch=320, **kwargs):
+                 max_prompts_per_launch=320, mm_num_repeats=None, **kwargs):
         super().__init__()
         self.cfg = cfg
         self.datamodule = datamodule
@@ -87,6 +87,8 @@ class LADIFF(nn.Module):
         self.max_it = int(pick(max_it, abl, "MAX_IT", 5))
         self.frame_per_latent = int(pick(frame_per_latent, abl, "FRAME_PER_LATENT", 48))
         self.test_efficiency = bool(pick(test_efficiency, abl, "TEST_EFFICIENCY", False))
+        # motions generated per prompt in the multimodality pass (cfg.TEST.MM_NUM_REPEATS, ladiff.py:1122-1132; configs/base.yaml: 30)
+        self.mm_num_repeats = int(pick(mm_num_repeats, _cfg_get(cfg, "TEST"), "MM_NUM_REPEATS", 30))
         if _cfg_get(cfg, "ARDIFF", False) or _cfg_get(abl, "JOINT_DISTRO_FIX", False):
             raise NotImplementedError("ARDIFF / JOINT_DISTRO_FIX branches of _diffusion_reverse are not built")
         self.denoiser = denoiser if denoiser is not None else instantiate_from_config(_cfg_get(model, "denoiser"))
@@ -641,6 +643,8 @@ class LADIFF(nn.Module):
         if self.text_encoder is None or not hasattr(self.datamodule, "renorm4t2m"):
             raise RuntimeError("t2m_eval needs a text_encoder and datamodule.renorm4t2m / feats2joints")
         self._check_loaded_weights()
+        if getattr(self.datamodule, "is_mm", False):                                  # ladiff.py:1122-1132
+            return self._t2m_eval_mm(batch, self.mm_num_repeats)
         texts, lengths = list(batch["text"]), [int(l) for l in batch["length"]]
         dev = self.device
         motions = batch["motion"].detach().clone().to(dev)
@@ -665,6 +669,155 @@ class LADIFF(nn.Module):
         text_lat = self.t2m_textencoder(batch["word_embs"].to(dev), batch["pos_ohot"].to(dev), batch["text_len"])[idx]
         return {"m_ref": motions, "m_rst": feats_rst, "lat_t": text_lat, "lat_m": motion_emb, "lat_rm": recons_emb,
                 "joints_ref": joints_ref, "joints_rst": joints_rst}
+
+    # ------------------------------------------------------------------ multimodality pass
+    def _expanded_text(self, encoded, row_of_sample):
+        """[2N,1,768] (guidance: the "" row N times, then sample i's prompt row) or [N,1,768] from `encoded` = text_encoder(["", distinct
+        prompts...]) resp. text_encoder(distinct prompts): row indexing in the library (`ladiff_gather_rows`), no arithmetic."""
+        if self.do_classifier_free_guidance:
+            rows = [0] * len(row_of_sample) + [1 + r for r in row_of_sample]
+        else:
+            rows = list(row_of_sample)
+        return _lib.gather_rows(encoded.detach().to(device=self.device, dtype=torch.float32).contiguous(), rows)
+
+    def _encode_distinct(self, texts):
+        """The text encoder on the DISTINCT prompts only (with guidance: "" first) -> (embeddings, row of every entry of `texts`)."""
+        distinct = list(dict.fromkeys(texts))
+        where = {t: i for i, t in enumerate(distinct)}
+        encoded = self.text_encoder([""] + distinct if self.do_classifier_free_guidance else distinct)
+        return encoded, [where[t] for t in texts]
+
+    def _t2m_eval_mm(self, batch, R):
+        """`t2m_eval` with `datamodule.is_mm` set (ladiff.py:1122-1132): every entry of the batch repeated R = MM_NUM_REPEATS times the way
+        the reference repeats it - `text` and `length` as `list * R` (sample i: entry i % B), `motion`, `word_embs`, `pos_ohot`, `text_len`
+        with `repeat_interleave` (sample i: entry i // R); the reference's MM loader gives B = 1, where the two agree.  Same `rs_set` as
+        `t2m_eval`, B * R rows.  The duplicates are not computed: the text encoder sees the distinct strings, the evaluators every distinct
+        ground-truth (motion, length) and caption once; rows are then repeated by indexing."""
+        texts0, lengths0 = list(batch["text"]), [int(l) for l in batch["length"]]
+        B = len(texts0)
+        N = B * R
+        dev = self.device
+        lengths = lengths0 * R
+        src = [i // R for i in range(N)]
+        src_t = torch.as_tensor(src, device=dev)
+        motions0 = batch["motion"].detach().clone().to(dev)
+        start = time.time()
+        encoded, row_of_text = self._encode_distinct(texts0)
+        text_emb = self._expanded_text(encoded, [row_of_text[i % B] for i in range(N)])
+        z = self._diffusion_reverse(text_emb, lengths)
+        with torch.no_grad():
+            feats_rst = self.vae.decode(z, lengths)
+        torch.cuda.synchronize()
+        self.check()
+        self.times.append(time.time() - start)
+        f2j = self.feats2joints_device or (lambda f: self.feats2joints(f.detach().cpu()))
+        joints_rst, joints_ref0 = f2j(feats_rst), f2j(motions0)
+        joints_ref = joints_ref0[src_t.to(joints_ref0.device)]
+        feats_rst = self.datamodule.renorm4t2m(feats_rst)
+        motions0 = self.datamodule.renorm4t2m(motions0)
+        align = np.argsort(lengths)[::-1].copy()
+        idx = torch.as_tensor(align, device=dev)
+        feats_rst = feats_rst[idx]
+        m_lens = torch.tensor(lengths, device=dev)[idx] // self.t2m_unit_len
+        recons_emb = self.t2m_motionencoder(self.t2m_moveencoder(feats_rst[..., :-4]), m_lens)
+        pairs, pair_of = {}, []                                # distinct (ground-truth motion, length) pairs: one for B = 1
+        for i in range(N):
+            pair_of.append(pairs.setdefault((src[i], lengths[i]), len(pairs)))
+        keys = list(pairs)
+        gt = motions0[torch.as_tensor([k[0] for k in keys], device=dev)]
+        gt_lens = torch.tensor([k[1] for k in keys], device=dev) // self.t2m_unit_len
+        motion_emb = self.t2m_motionencoder(self.t2m_moveencoder(gt[..., :-4]), gt_lens)[torch.as_tensor(pair_of, device=dev)[idx]]
+        text_lat = self.t2m_textencoder(batch["word_embs"].to(dev), batch["pos_ohot"].to(dev), batch["text_len"])[src_t[idx]]
+        return {"m_ref": motions0[src_t[idx]], "m_rst": feats_rst, "lat_t": text_lat, "lat_m": motion_emb, "lat_rm": recons_emb,
+                "joints_ref": joints_ref, "joints_rst": joints_rst}
+
+    def _mm_launches(self, B, R, prompts_per_launch=None):
+        """[lo, hi) PROMPT ranges of the loop launches of `mm_eval`: whole prompts only, balanced, each launch at most
+        `max_prompts_per_launch` motions (320 = 10 prompts x 30 repeats) and at most `prompts_per_launch` prompts when given.  A single
+        prompt with more repeats than the cap is one range (the loop then cuts its samples, `_chunks`)."""
+        cap = self.max_prompts_per_launch
+        per = B if cap is None else max(1, int(cap) // max(1, R))
+        if prompts_per_launch is not None:
+            per = min(per, max(1, int(prompts_per_launch)))
+        per = max(1, min(per, B))
+        n = -(-B // per)
+        base, extra = divmod(B, n)
+        spans, lo = [], 0
+        for i in range(n):
+            hi = lo + base + (1 if i < extra else 0)
+            spans.append((lo, hi))
+            lo = hi
+        return spans
+
+    def mm_eval(self, batch, repeats=None, prompts_per_launch=None, *, init_noise=None, noise_seed=None):
+        """The multimodality pass, batched: R = `repeats` (default MM_NUM_REPEATS) motions for each of the B >= 1 prompts of `batch`
+        (keys `text`, `length`) -> {"lat_rm": [B, R, 512] evaluator embeddings IN THE CALLER'S PROMPT ORDER, "m_rst": [B*R, max(length),
+        nfeats] renormalised features, "joints_rst", "lengths": list of B*R ints}; sample prompt * R + repeat is repeat `repeat` of prompt
+        `prompt`, so `MMMetrics.update(rs["lat_rm"], rs["lengths"])` is all a caller adds.  What the reference does as one `t2m_eval`
+        call of 30 rows per prompt (ladiff.py:1122-1132) runs here as loop launches of several whole prompts (`_mm_launches`), and every
+        distinct prompt is encoded once.
+
+        A result does not depend on how the prompts are packed: the initial noise is ONE `torch.randn(B*R, T, 256)` for the whole call
+        (or `init_noise`), sliced per launch, and for the stochastic schedules (DDPM, eta > 0) the device generator is keyed by the
+        sample index (`noise_first_prompt` + prompt * R + repeat) with one `noise_seed` for the call - up to the rounding of another
+        block packing inside the loop.  The evaluators see every prompt's R motions as a batch of that prompt's own
+        length, as the reference's one-prompt MM batches do (the movement encoder's last output looks one frame past the length, so its
+        value depends on the padding); there is no longest-first sort to undo."""
+        if getattr(self, "t2m_motionencoder", None) is None:
+            raise RuntimeError("call set_t2m_evaluators(text_encoder, movement_encoder, motion_encoder) first")
+        if self.text_encoder is None or not hasattr(self.datamodule, "renorm4t2m"):
+            raise RuntimeError("mm_eval needs a text_encoder and datamodule.renorm4t2m / feats2joints")
+        if self.test_efficiency:
+            raise NotImplementedError("mm_eval with TEST_EFFICIENCY (a latent count per launch) is not built")
+        self._check_loaded_weights()
+        R = int(self.mm_num_repeats if repeats is None else repeats)
+        texts0, lengths0 = list(batch["text"]), [int(l) for l in batch["length"]]
+        B = len(texts0)
+        if B < 1 or R < 1 or len(lengths0) != B:
+            raise ValueError("mm_eval needs B >= 1 prompts with one length each and repeats >= 1")
+        N, T, dev = B * R, self.max_it, self.device
+        lengths = [l for l in lengths0 for _ in range(R)]
+        if init_noise is None:
+            init_noise = torch.randn(N, T, 256, device=dev, dtype=torch.float32)
+        elif tuple(init_noise.shape) != (N, T, 256):
+            raise ValueError(f"init_noise {tuple(init_noise.shape)} for {N} samples x {T} latents")
+        if noise_seed is None:
+            noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        start = time.time()
+        encoded, row_of_text = self._encode_distinct(texts0)
+        feats = None
+        base = int(self.noise_first_prompt)
+        self.last_mm_launches = self._mm_launches(B, R, prompts_per_launch)
+        try:
+            for lo, hi in self.last_mm_launches:
+                s0, s1 = lo * R, hi * R
+                text_emb = self._expanded_text(encoded, [row_of_text[i // R] for i in range(s0, s1)])
+                self.noise_first_prompt = base + s0
+                z = self._diffusion_reverse(text_emb, lengths[s0:s1], init_noise=init_noise[s0:s1], noise_seed=noise_seed)
+                with torch.no_grad():
+                    part = self.vae.decode(z, lengths[s0:s1])
+                if feats is None:
+                    feats = torch.zeros(N, max(lengths0), part.shape[-1], dtype=part.dtype, device=dev)
+                feats[s0:s1, :part.shape[1]] = part
+        finally:
+            self.noise_first_prompt = base
+        torch.cuda.synchronize()
+        self.check()
+        self.times.append(time.time() - start)
+        f2j = self.feats2joints_device or (lambda f: self.feats2joints(f.detach().cpu()))
+        joints_rst = f2j(feats)
+        m_rst = self.datamodule.renorm4t2m(feats)
+        lat_rm = torch.empty(B, R, 512, dtype=torch.float32, device=dev)
+        by_len = {}
+        for b, l in enumerate(lengths0):
+            by_len.setdefault(l, []).append(b)
+        rep = torch.arange(R, device=dev)
+        for l, prompts in by_len.items():
+            rows = (torch.as_tensor(prompts, device=dev)[:, None] * R + rep[None]).reshape(-1)
+            m_lens = torch.full((rows.numel(),), l // self.t2m_unit_len, dtype=torch.int64, device=dev)
+            emb = self.t2m_motionencoder(self.t2m_moveencoder(m_rst[rows, :l, :-4]), m_lens)
+            lat_rm[torch.as_tensor(prompts, device=dev)] = emb.reshape(len(prompts), R, 512)
+        return {"lat_rm": lat_rm, "m_rst": m_rst, "joints_rst": joints_rst, "lengths": lengths}
 
     def recon_from_motion(self, batch):
         """encode -> decode -> joints of the reconstruction and of the input (ladiff.py:320-331)."""
