@@ -1,37 +1,47 @@
-// The denoiser loop as ONE persistent, weight-stationary pipeline over the whole chip (f16x3 mode, guidance on).
+// The denoiser loop as ONE persistent, weight-stationary pipeline over the whole chip (guidance on; both arithmetic modes).
 //
 // Why: a guided DDIM step is 9 layers x ~8 dependent matrix stages on only M = 2*B*T = 1280 rows.  As separate launches
 // (denoiser.hip: 77 per step) every stage costs a kernel boundary, a ramp-up in which each of ~256 workgroups re-fetches
 // its weight tile from the Infinity Cache, a few hundred MFMA cycles and a ramp-down: 7 us per stage, 550 us per step, 4 %
 // of the MFMA peak (profiles/r1).  Here the roles are turned around.  Every CU is ONE stage of the network for the whole
 // loop and keeps its slice of the weights in REGISTERS (all in-loop weights are 51 MB in S-format; the chip has 128 MB of
-// VGPRs): 27 CUs per layer -
-//     QKV  x4  in_proj rows of one head (192x256) + the 7-key attention of that head     mdiff_transformer.py:57-61, :296-313
-//     OUT  x1  attention out-projection + residual + norm1                               :62-63
-//     LIN  x8  linear1 (128 hidden columns, ReLU) + that slice's part of linear2          :64
-//     RED2 x3  sum of the 8 partial products + bias + residual + norm2 + hoisted ca_block :65-66, :219-247
-//     FFN  x8  ffn.linear1 (128 columns, GELU) + that slice's part of ffn.linear2         :259-260
-//     STYL x3  sum of the 8 partials + StylizationBlock (LN, AdaLN, SiLU, 256x256 out) + residual   :152-162, :261
-// - plus SKIP x2 on the four output layers (linear_blocks on cat(x, skip), cross_attention.py:79-82) and one TAIL CU
-// (encoder.norm, guidance, scheduler step, next input: ladiff.py:472-492).  The ACTIVATIONS flow: the batch is cut into
-// blocks of P prompts (both guidance branches, 2*P*T <= 32 rows = two MFMA row tiles); a block's rows travel from stage to
-// stage through global memory, and every block is at a different stage, so all stages work at once.  Prompts never mix
-// (attention is per sample, LayerNorm per row, guidance pairs the two branches of one prompt), so a block needs nothing
-// but its own previous stage - there is no grid-wide barrier anywhere, and the 50 steps are one launch.
+// VGPRs).  The plan that ships (16-row blocks, 512-thread workgroups: sys_build_stages, red_plan) has 27 workgroups per layer -
+//     QKV  x4   in_proj rows of one head (192x256) + the 7-key attention of that head     mdiff_transformer.py:57-61, :296-313
+//     OUT  x1   attention out-projection + residual + norm1                               :62-63
+//     LIN  x8   linear1 (128 hidden columns, ReLU) + that slice's part of linear2          :64
+//     RED2 x2   (row parts) sum of the 8 partial products + bias + residual + norm2 + hoisted ca_block   :65-66, :219-247
+//     FFN  x8   ffn.linear1 (128 columns, GELU) + that slice's part of ffn.linear2         :259-260
+//     STYL 2x2  (two groups on alternating blocks x two row parts) sum of the 8 partials + StylizationBlock (LN, AdaLN, SiLU,
+//               256x256 out) + residual                                                    :152-162, :261
+// - plus SKIP x2 on the four output layers (linear_blocks on cat(x, skip), cross_attention.py:79-82) and 4 TAIL workgroups (block b
+// belongs to tail b % 4: encoder.norm, guidance, scheduler step, next input: ladiff.py:472-492): 255 workgroups, one per CU.  The
+// ACTIVATIONS flow: the batch is cut into 16-row blocks (ONE guidance branch of as many prompts as fit with only their valid latent
+// rows = one MFMA row tile; BlockDesc); a block's rows travel from stage to stage through global memory, and every block is at a
+// different stage, so all stages work at once.  Prompts never mix (attention is per sample, LayerNorm per row, the tail joins the
+// two branches of one prompt), so a block needs nothing but its own previous stage - there is no grid-wide barrier anywhere,
+// and the 50 steps are one launch.  The 32-row plan (both branches in a block, 256-thread workgroups, RED2 x3 / STYL x3) remains for
+// calls whose latent counts exist on the device only.
 //
-// Hand-off (MI355X_MICROARCH.md "inter-workgroup visibility", cdna_hip_programming.md G16 R1): the eight L2s are not
-// coherent, so a producer stores its rows write-through (`buffer_store ... sc1`), every storing wave drains
-// (`s_waitcnt vmcnt(0)`), the workgroup meets at a barrier, and ONE lane publishes an epoch in a flag word (agent-scope
-// relaxed store); the consumer's wave 0 polls that word (agent-scope relaxed loads, `s_sleep` between polls), the
-// workgroup meets at a barrier, and EVERY load of handed-off bytes is a `buffer_load ... sc1` to registers (never LDS-DMA,
-// never a plain load).  Epoch = local step + 1; flag words are zeroed by a memset node before every launch.  A buffer is
-// rewritten one step later, by which time its consumer has long finished with it (the rewrite depends on it through the
-// chain of flags), so there is no back-pressure channel.  Every spin is bounded (wall clock); a timeout raises an abort word
-// that all pollers watch, and the host reports it.
+// Hand-off, the default (HO = 1 / 2, "tagged": see tag4 below): the DATA carries the epoch.  The last mantissa bit of every fp32
+// word of a handed-off row is a parity bit (of the local step for buffers written once per step, of the slot's use count for the
+// rings of partial planes); a consumer loads the rows it needs (`buffer_load ... sc1` to registers, never LDS-DMA), looks at the bit
+// of every word and loads again until all show the parity it expects, then clears the bits and computes.  No drain, no barrier, no
+// flag store, no separate poll.  A stage whose readers all share its XCD's L2 stores plainly (HO = 2), the others write through
+// (`sc1`, HO = 1): the eight L2s are not coherent (MI355X_MICROARCH.md "inter-workgroup visibility", cdna_hip_programming.md G16 R1).
+// THE INVARIANT the one-bit tag rests on: NO CONSUMER WAVE IS EVER AHEAD OF THE PRODUCER OF ITS RING, and no producer is more than one
+// ring (PRING blocks) ahead of its consumer - so a reader only ever sees a slot's previous use (other parity: it waits) or the awaited
+// one, never the use before last, which one bit could not tell from the awaited one.  Every stage with a barrier and every live row
+// has the first half by construction; padding rows of barrier-free stages wait for their ring's producers explicitly
+// (Red2Role::issue); the second half is MlpRole::backpressure_tag.  The constants it depends on are checked next to PRING.
+// The flag protocol (HO = 0: write-through stores, `s_waitcnt vmcnt(0)`, barrier, an epoch word per producer that the consumer
+// polls; wait_epoch / publish) is the only form of the 32-row plan and the run-time fallback (ladiff_debug_set_handoff(0)); it stores
+// and clears the same bit, so the two protocols give the same bits.  Every spin is bounded (wall clock); a timeout raises an abort
+// word that all pollers watch, and the host reports it.
 //
-// Numerics: the same arithmetic as the launch-per-stage f16x3 path (S-format operands, hi*hi + hi*lo + lo*hi on
-// v_mfma_f32_16x16x32_bf16, fp32 accumulation and fp32 everything else); only the summation order of the split products
-// differs (8 hidden slices instead of 4 K-slices).
+// Numerics: the same arithmetic as the launch-per-stage path.  Split mode ("f16x3", AR = 0): S-format operands = hi + lo pairs of
+// fp16 halves (bf16 halves in the -DLADIFF_SPLIT_BF16 build), hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 (_bf16), fp32
+// accumulation and fp32 everything else; AR = 1 is the fp32 mode.  Only the summation order of the split products differs from the
+// launch-per-stage loop (8 hidden slices instead of 4 K-slices).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +83,13 @@ constexpr int FLAG_SLOTS = 16;
 // block b of local step s is (s NB + b) % PRING: blocks are counted THROUGH the steps, so that the reuse distance is PRING
 // blocks at the wrap from one step to the next as well.
 constexpr int PRING = 16;
+// What the one-bit tag of a ring slot needs from these constants (the invariant in the header of this file).  A producer looks back
+// every PRING / 2 blocks, at the consumer's block PRING / 2 back and - where the consumer is MAX_BP_BLOCKS groups on alternating
+// blocks - at the blocks just before it: the look-back must be a whole number of blocks, and every block it looks at must lie
+// inside the ring's previous half, so that "the consumer has finished them" covers exactly the slots the next PRING / 2 blocks overwrite.
+constexpr int MAX_BP_BLOCKS = 2;            // consecutive blocks that make "all consumers" (Stage::bp_blocks <= this: red_plan's styl_groups)
+static_assert(PRING >= 2 && PRING % 2 == 0, "the back-pressure look-back is PRING / 2 blocks");
+static_assert(MAX_BP_BLOCKS <= PRING / 2, "every block a producer looks back at must be in the half ring it is about to leave alone");
 constexpr int SMALL_LAUNCH_BLOCKS = 60;     // launches up to this many blocks: LIN / FFN rest after every block (launch_systolic_loop)
 constexpr int PACED_ROLES = 4;              // stage types (R::PAUSE_BIT) whose polling is paced (tag_loop): STYL
 constexpr int FLAG_STRIDE = 32;             // words between the flags of two producers: every flag on a 128-byte line of its own
@@ -104,6 +121,25 @@ struct Stage {                            // one per workgroup
     const float* bp_buf;                  // LIN / FFN, tagged hand-off: the consumer's OUTPUT rows (their tags are the ring's back-pressure)
 };
 
+// The workgroup's Stage arrives as a few wide scalar loads (s_load_dwordx16): sixteen-register tuples.  The register allocator keeps a
+// tuple whole - the roles' buffer resources were even built IN one (its dead words reused for the resource's constant words) - and the
+// block loops run at the 104-SGPR ceiling, so wherever one word of a spilled tuple was needed (a resource's base in front of a block's row
+// loads) all sixteen came back through v_readlane, on the wave's serial chain: 15 of FFN's 44 restores per block stood between the tile
+// barrier and the first MFMA, QKV's loader waves restored the tuple eight times per block (round 7, scripts/loop_isa_audit.py).  Passing
+// every field through an empty asm gives it a scalar register (pair) of its own: what is spilled and restored is then the one value.
+template <class T>
+__device__ __forceinline__ void own_sgpr(T& v) { asm volatile("" : "+s"(v)); }
+__device__ __forceinline__ void own_stage(Stage& st) {
+    own_sgpr(st.role); own_sgpr(st.layer); own_sgpr(st.slice); own_sgpr(st.act);
+    own_sgpr(st.wait_group); own_sgpr(st.wait_n); own_sgpr(st.out_group); own_sgpr(st.out_slot);
+    own_sgpr(st.blk0); own_sgpr(st.blkstride);
+    own_sgpr(st.wait_slot0); own_sgpr(st.out_rep); own_sgpr(st.out_rep_stride);
+    own_sgpr(st.out_local); own_sgpr(st.xcd);
+    own_sgpr(st.bp_group); own_sgpr(st.bp_slot0); own_sgpr(st.bp_n); own_sgpr(st.bp_blocks);
+    own_sgpr(st.w0); own_sgpr(st.w1); own_sgpr(st.b0); own_sgpr(st.b1); own_sgpr(st.g); own_sgpr(st.be);
+    own_sgpr(st.in0); own_sgpr(st.in1); own_sgpr(st.in2); own_sgpr(st.out); own_sgpr(st.bp_buf);
+}
+
 // Geometry of one block, built on the host (sys_pack_blocks).  32-row tiles: both guidance branches of P prompts, T rows each
 // (the latent count masks keys).  16-row tiles: ONE guidance branch of as many prompts as fit with only their count[b] valid
 // latent rows (length-aware: padded latent rows never influence valid ones - they are masked as keys, every other op is
@@ -133,9 +169,12 @@ static_assert(NRED == 3, "BlockDesc::part_pk");
 struct RedPlan { int red2_parts, styl_parts, styl_groups, out_groups; };
 // how a layer's workgroups that hold no MLP slice are dealt (16-row blocks): variant 0 = one OUT workgroup, STYL as two groups on
 // alternating blocks x two row parts; variant 1 = OUT as two groups on alternating blocks, STYL as one group x two row parts
+constexpr RedPlan PLAN32{NRED, NRED, 1, 1}, PLAN16{2, 2, 2, 1}, PLAN16_OUT2{2, 2, 1, 2};
+static_assert(PLAN32.styl_groups <= MAX_BP_BLOCKS && PLAN16.styl_groups <= MAX_BP_BLOCKS && PLAN16_OUT2.styl_groups <= MAX_BP_BLOCKS,
+              "a ring's producer looks back at styl_groups consecutive blocks (Stage::bp_blocks): see PRING");
 inline RedPlan red_plan(int MR) {
-    if (MR != 1) return RedPlan{NRED, NRED, 1, 1};
-    return g_stage_plan.load() == 1 ? RedPlan{2, 2, 1, 2} : RedPlan{2, 2, 2, 1};
+    if (MR != 1) return PLAN32;
+    return g_stage_plan.load() == 1 ? PLAN16_OUT2 : PLAN16;
 }
 
 struct SysArgs {
@@ -2198,6 +2237,10 @@ __global__ __launch_bounds__(256 * WS, 1) void systolic_loop_kernel(const SysArg
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     Ctl* const ctl = reinterpret_cast<Ctl*>(lds + SYS_LDS_BYTES - 16);
     Stage st = p.stages[blockIdx.x];
+    // (the look-ahead instantiation only: launches in which a block's trip bounds the step run the other one, and there the shorter
+    // chains measured +0.4 % on the loop - stages that poll faster on the lines a critical-path stage is still storing to, as with
+    // every other attempt to speed up single stages of a trip-bound launch - so those launches keep exactly the code they had)
+    if constexpr (EQ) own_stage(st);
     if (threadIdx.x == 0) {
         ctl->abort = 0; ctl->ready = 0; ctl->arrive = 0u; ctl->local_ok = 1;
         // the abort word is STICKY over the launches of one ladiff_diffusion_reverse call (a long schedule runs window by window:
