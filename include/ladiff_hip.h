@@ -27,6 +27,15 @@
  *       ladiff_sampler_loop_ms       hipEventSynchronize on the loop's end event
  *       ladiff_reverse_status        blocking hipMemcpy (use ladiff_reverse_status_offset_bytes + an async copy to poll)
  *       the first pipeline launch on a device  runs a probe kernel on a private stream (hipMalloc / hipFree / stream create)
+ *   - workspaces: a workspace AT LEAST as large as the matching *_workspace_bytes query is sufficient (a larger one gives the
+ *     same results), and every *_workspace_bytes query is non-decreasing in each of its size arguments (batch, rows, frames,
+ *     latents, steps, text tokens): a caller may size one workspace for its largest call and use it for every smaller one.  (The
+ *     *_floats queries size caller-held RESULTS, whose layout follows their arguments exactly: ladiff_denoiser_text_cache_floats
+ *     has one layout for n_text == 1 and another for n_text > 1 and is not ordered across the two.)  An entry refuses
+ *     (LADIFF_ERR_WORKSPACE, nothing enqueued, no output touched) a workspace below the query at its own arguments - for the three
+ *     denoiser entries, which share ladiff_denoiser_workspace_bytes and take only some of its arguments, with the missing ones at 1.
+ *     Except where an entry says otherwise (ladiff_diffusion_reverse) a workspace is pure scratch: no result depends on what it held
+ *     before the call, and nothing in it needs to survive the call.
  *   - tensors are dense row-major fp32.  Arithmetic: w_split == NULL -> fp32-input MFMA, fp32 accumulate (exact fp32
  *     fma chains inside every product; the persistent pipeline kernel of ladiff_diffusion_reverse additionally clears the last
  *     mantissa bit of every activation word it hands from one stage to the next - the bit carries the hand-off's parity tag,
@@ -270,6 +279,16 @@ LADIFF_API int ladiff_finalize_latents(const float* latents, const int32_t* coun
  *                keys, every other op is per row, and the final zeroing removes them)
  * reuse_time_tables = 1 tells the call that `ws` still holds the time tables of a previous call with the same weights
  * and schedule.
+ * What the workspace holds between calls:
+ *   sampler == NULL, reuse_time_tables == 0: nothing - `ws` is pure scratch, its contents before the call do not matter and the caller
+ *     may overwrite or reuse it as soon as the call's work on `stream` has completed.
+ *   reuse_time_tables == 1: the time tables of the previous call (above); the caller must not have altered `ws` since.
+ *   with a sampler: `ws` also holds STATE OF THE SAMPLER'S CAPTURE KEY - the pipeline kernel's stage table (device pointers into the
+ *     weights and into `ws` itself), its block plan and the time tables - uploaded when the key changes (first call, or any pointer,
+ *     shape, scalar or weight table differs) and only read by later calls with the same key.  `ws` is part of the key.  Between two
+ *     calls with the same sampler the workspace MUST NOT be altered, copied elsewhere in place of the original, or lent to another
+ *     entry: a later call would hand the kernel a table of stale pointers.  Before the FIRST call of a fresh sampler (and after
+ *     ladiff_sampler_destroy) its contents do not matter.
  * Synchronisation / allocation: with sampler == NULL the call only enqueues.  With a sampler it instantiates graphs and creates
  * events on first use, calls hipStreamSynchronize(stream) whenever its capture key changes (before the old graphs are destroyed,
  * after a new stage table is uploaded, before a changed block plan replaces the previous host copy), and a pipeline launch takes

@@ -37,13 +37,19 @@ struct ReverseWs {
 };
 // The hoisted cross-attention table is [9][steps][2B+1][256] floats: 118 MB for 50 steps at B = 128, but 2.4 GB for a
 // 1000-step DDPM schedule.  Long schedules are run window by window (the largest divisor of n_steps that is <= 64 and a
-// multiple of the graph unroll), the table rebuilt before each window from the per-layer LN(value) rows kept in the cache.
+// multiple of 10, so that the step graphs unroll ten-fold; failing that the largest divisor <= 64 of any kind), the table rebuilt
+// before each window from the per-layer LN(value) rows kept in the cache.  A window never exceeds REVERSE_WINDOW_MAX steps, and the
+// carve reserves the table for min(n_steps, REVERSE_WINDOW_MAX) steps whatever the window: the workspace query is then non-decreasing
+// in n_steps (a 65-step schedule used to keep a 65-step table and ask for more than a 1000-step one).  A schedule longer than 64 steps
+// with few divisors pays in table rebuilds (a prime length rebuilds per step), not in memory.
+constexpr int REVERSE_WINDOW_MAX = 64;
 int reverse_window(int n) {
-    if (n <= 64) return n;
-    int best = 0;
-    for (int w = 64; w >= 10; --w)
-        if (n % w == 0 && w % 10 == 0) { best = w; break; }
-    return best > 0 ? best : n;
+    if (n <= REVERSE_WINDOW_MAX) return n;
+    for (int w = REVERSE_WINDOW_MAX; w >= 10; --w)
+        if (n % w == 0 && w % 10 == 0) return w;
+    for (int w = REVERSE_WINDOW_MAX; w > 1; --w)
+        if (n % w == 0) return w;
+    return 1;
 }
 ReverseWs carve_reverse(void* ws, int B, int T, int n, int ntxt = 1) {
     ReverseWs r;
@@ -53,7 +59,8 @@ ReverseWs carve_reverse(void* ws, int B, int T, int n, int ntxt = 1) {
     r.d_step = reinterpret_cast<int32_t*>(take(64));
     r.tables = take(den_tables_floats(n));
     r.window = reverse_window(n);
-    r.cache = take(den_text_cache_floats(B2, r.window, ntxt));
+    const int wcap = n < REVERSE_WINDOW_MAX ? n : REVERSE_WINDOW_MAX;  // >= r.window; sized by it so that the query never shrinks with n
+    r.cache = take(den_text_cache_floats(B2, wcap, ntxt));             // the c table is the cache's last part: r.window steps of it are used
     r.latents = take((size_t)B * T * D);
     r.eps = take((size_t)B2 * T * D);
     size_t pre = (size_t)n * D * 3;                                    // time-table scratch
@@ -64,7 +71,7 @@ ReverseWs carve_reverse(void* ws, int B, int T, int n, int ntxt = 1) {
     r.fwd = take(r.fwd_floats);
     r.sys_off = off;
     r.sys = take(sys_ws_floats(B, T));                                 // block buffers, flags and stage table of the pipeline loop
-    r.cws_floats = (size_t)NL * r.window * (B2 + 1) * D;               // scratch of the c-table builder (all layers' input rows)
+    r.cws_floats = (size_t)NL * wcap * (B2 + 1) * D;                   // scratch of the c-table builder (all layers' input rows)
     r.cws = take(r.cws_floats);
     r.total_bytes = off * sizeof(float);
     return r;
@@ -279,13 +286,19 @@ size_t ladiff_denoiser_workspace_bytes(int B2, int T, int n_steps, int n_text) {
     const size_t a = (size_t)n_steps * D * 3, b = den_text_ws_floats(B2, n_steps, n_text);
     if (a > f) f = a;
     if (b > f) f = b;
+    // n_text > 1 switches the text cache to another algorithm with less scratch: never less than the one-token form asks for, so that the
+    // query is non-decreasing in every argument
+    if (n_text > 1) { const size_t c = den_text_ws_floats(B2, n_steps, 1); if (c > f) f = c; }
     return f * sizeof(float);
 }
+// The three denoiser entries share one query, but none of them takes all of its arguments: each refuses a workspace below the query at
+// its OWN arguments (the ones it does not take at 1).  The query is non-decreasing, so this is never more than the caller's query.
 
 int ladiff_denoiser_time_tables(const float* const* w, const float* sinusoid, int n_steps, float* tables, void* ws,
                                 size_t ws_bytes, ladiff_stream_t stream) {
     DenoiserW W;
     LADIFF_CHECK_ARG(load_weights(W, w) && sinusoid && tables && ws && n_steps > 0);
+    if (ws_bytes < ladiff_denoiser_workspace_bytes(1, 1, n_steps, 1)) return LADIFF_ERR_WORKSPACE;
     return denoiser_time_tables(W, sinusoid, n_steps, tables, (float*)ws, ws_bytes / sizeof(float), S(stream));
 }
 
@@ -293,6 +306,7 @@ int ladiff_denoiser_text_cache(const float* const* w, const float* text_emb, int
                                float* cache, void* ws, size_t ws_bytes, ladiff_stream_t stream) {
     DenoiserW W;
     LADIFF_CHECK_ARG(load_weights(W, w) && text_emb && tables && cache && ws && B2 > 0 && n_steps > 0 && n_text >= 1);
+    if (ws_bytes < ladiff_denoiser_workspace_bytes(B2, 1, n_steps, n_text)) return LADIFF_ERR_WORKSPACE;
     return denoiser_text_cache(W, text_emb, B2, tables, n_steps, cache, (float*)ws, ws_bytes / sizeof(float), S(stream), n_text);
 }
 
@@ -303,6 +317,8 @@ int ladiff_denoiser_forward(const float* const* w, const float* const* w_split, 
     LADIFF_CHECK_ARG(load_weights(W, w) && tables && d_step && text_cache && sample && eps && ws && Bs > 0 && dup > 0 && n_steps > 0 &&
                      n_text >= 1);
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
+    if (T < 1 || T > LADIFF_MAX_LATENTS) return LADIFF_ERR_SHAPE;
+    if (ws_bytes < ladiff_denoiser_workspace_bytes(Bs * dup, T, n_steps, n_text)) return LADIFF_ERR_WORKSPACE;
     return denoiser_forward(W, w_split ? &WS : nullptr, tables, d_step, text_cache, n_steps, sample, Bs, dup, T, counts, eps, (float*)ws,
                             ws_bytes / sizeof(float), S(stream), 0, -1, 0, n_text);
 }
@@ -929,6 +945,8 @@ int ladiff_vae_decode_graphed(void* graph, const float* const* w, const float* c
     DecoderW W, WS;
     LADIFF_CHECK_ARG(dg && load_weights(W, w) && z && lengths && feats && ws && B >= 0 && stream != nullptr);
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
+    if (F < 1 || F > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;      // as the ragged entry
+    if (ws_bytes < ladiff_decoder_workspace_bytes(B, F, T, C)) return LADIFF_ERR_WORKSPACE;
     hipStream_t s = S(stream);
     const void* kp[7] = {z, lengths, counts, row_off, feats, ws, stream};
     const int ki[6] = {B, F, T, C, total_rows, w_split ? 1 : 0};
@@ -976,6 +994,9 @@ int ladiff_vae_decode_ragged(const float* const* w, const float* const* w_split,
     DecoderW W, WS;
     LADIFF_CHECK_ARG(load_weights(W, w) && z && lengths && row_off && feats && ws && B >= 0 && total_rows >= 0);
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
+    // the documented size is the padded batch's (the ragged rows need less): refused below it, and before feats is touched
+    if (F < 1 || F > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;
+    if (ws_bytes < ladiff_decoder_workspace_bytes(B, F, T, C)) return LADIFF_ERR_WORKSPACE;
     // frames past each length: zero, whatever the buffer held (ladiff_vae.py:356-360)
     LADIFF_HIP(hipMemsetAsync(feats, 0, (size_t)B * F * C * sizeof(float), S(stream)));
     return vae_decode(W, w_split ? &WS : nullptr, z, lengths, counts, row_off, total_rows, B, F, T, C, feats, (float*)ws,

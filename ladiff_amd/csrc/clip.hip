@@ -133,9 +133,13 @@ constexpr int CLIP_PLANE_COLS = 12 * CW;       // floats per row of the partial 
 // blockIdx.y (GemmArgs::ksplit: four times the workgroups, two per CU hiding each other's stages) and the row pass sums the planes.
 constexpr int CLIP_FC2_KPARTS = 4;
 constexpr int CLIP_FC2_KPARTS_MAX_ROWS = 8192;  // beyond, the tiles alone fill the chip
+// Plane space for M rows: the largest need of any regime a call with AT MOST M rows can land in (small-row planes up to CLIP_SMALL_ROWS
+// rows, fc2's K parts up to CLIP_FC2_KPARTS_MAX_ROWS, none beyond), so that the workspace query never shrinks when the row count grows: a
+// caller that sizes its workspace once for its largest batch is served at every smaller one.  The carve below takes the same amount.
 static size_t clip_plane_floats(int M) {
-    if (M <= CLIP_SMALL_ROWS) return (size_t)M * CLIP_PLANE_COLS;
-    return M <= CLIP_FC2_KPARTS_MAX_ROWS ? (size_t)M * CLIP_FC2_KPARTS * CW : 0;
+    const size_t small_rows = (size_t)(M < CLIP_SMALL_ROWS ? M : CLIP_SMALL_ROWS) * CLIP_PLANE_COLS;
+    const size_t kparts = M > CLIP_SMALL_ROWS ? (size_t)(M < CLIP_FC2_KPARTS_MAX_ROWS ? M : CLIP_FC2_KPARTS_MAX_ROWS) * CLIP_FC2_KPARTS * CW : 0;
+    return small_rows > kparts ? small_rows : kparts;
 }
 size_t clip_ws_floats_rows(int B, int M) {
     return (size_t)M * (2 * CW /*x ping-pong*/ + CW /*h*/ + 3 * CW /*qkv*/ + CW /*att*/ + CFF /*mlp*/) + (size_t)B * CW + (size_t)B + 64 +

@@ -93,6 +93,83 @@ def test_workspace_queries(lib):
     assert lib.ladiff_decoder_workspace_bytes(128, 196, 5, 263) >= 128 * 196 * 4096 * 4
 
 
+def _check_monotonic(name, fn, *axes, skip_axes=()):
+    import itertools
+    import numpy as np
+    shape = tuple(len(a) for a in axes)
+    v = np.fromiter((fn(*args) for args in itertools.product(*axes)), dtype=np.float64, count=int(np.prod(shape))).reshape(shape)
+    assert (v > 0).all(), name
+    for ax in range(len(axes)):
+        if ax in skip_axes or shape[ax] < 2:
+            continue
+        d = np.diff(v, axis=ax)
+        if (d < 0).any():
+            at = np.unravel_index(np.argmin(d), d.shape)
+            lo = [a[i] for a, i in zip(axes, at)]
+            hi = list(lo); hi[ax] = axes[ax][at[ax] + 1]
+            raise AssertionError(f"{name}{tuple(lo)} = {int(v[at])} but {name}{tuple(hi)} = {int(v[at] + d[at])}")
+
+
+
+def test_workspace_queries_are_monotonic(lib):
+    """include/ladiff_hip.h: every workspace query is non-decreasing in each of its arguments, so a caller that sizes a workspace once for
+    its largest call is served at every smaller one (host arithmetic only).  Before clip_plane_floats took the maximum over the regimes
+    reachable with at most M rows, the CLIP query for 257 rows was a third smaller than for 256 (256 x (8448 + 9216) floats against
+    257 x (8448 + 3072)) and a workspace sized for 300 rows was refused at 256.
+    `ladiff_denoiser_text_cache_floats` is the size of a caller-held RESULT whose two layouts (n_text == 1: the hoisted c table; n_text > 1:
+    the literal path's matrices) test_workspace_queries pins exactly: it is checked in B2 and n_steps for each n_text, not across them."""
+    check = _check_monotonic
+    r = lambda lo, hi: list(range(lo, hi + 1))
+    check("ladiff_clip_workspace_bytes_ragged", lib.ladiff_clip_workspace_bytes_ragged, [1, 4, 8], r(1, 9000))
+    check("ladiff_clip_workspace_bytes", lib.ladiff_clip_workspace_bytes, r(1, 128), r(1, 77))         # up to 9856 rows
+    check("ladiff_decoder_workspace_bytes", lib.ladiff_decoder_workspace_bytes, r(1, 140), r(1, 224), r(1, 8), [251, 263])
+    for T in r(1, 8):                                                                                  # F + 2T <= 224
+        check("ladiff_encoder_workspace_bytes", lambda B, F, C: lib.ladiff_encoder_workspace_bytes(B, F, T, C), r(1, 140), r(1, 224 - 2 * T),
+              [251, 263])
+    check("ladiff_encoder_workspace_bytes", lambda B, T, C: lib.ladiff_encoder_workspace_bytes(B, 100, T, C), r(1, 140), r(1, 8), [251, 263])
+    check("ladiff_denoiser_workspace_bytes", lib.ladiff_denoiser_workspace_bytes, r(1, 300), r(1, 8), [1, 5, 50], [1, 4])
+    check("ladiff_denoiser_text_cache_floats", lib.ladiff_denoiser_text_cache_floats, r(1, 300), [1, 5, 50], [1, 4], skip_axes=(2,))
+    check("ladiff_denoiser_tables_floats", lib.ladiff_denoiser_tables_floats, [1, 5, 50, 64, 65, 1000])
+    for n_text in (1, 4):                     # every n_steps up to 1100: test_reverse_workspace_query_is_monotonic_in_steps
+        check("ladiff_reverse_workspace_bytes", lambda B, T, n: lib.ladiff_reverse_workspace_bytes(B, T, n, n_text), r(1, 300), r(1, 8),
+              [1, 5, 50, 64, 65, 1000])
+    check("ladiff_t2m_movement_workspace_bytes", lib.ladiff_t2m_movement_workspace_bytes, r(1, 64), r(4, 224), [247, 259])
+    check("ladiff_t2m_motion_workspace_bytes", lib.ladiff_t2m_motion_workspace_bytes, r(1, 64), r(1, 56))
+    check("ladiff_t2m_text_workspace_bytes", lib.ladiff_t2m_text_workspace_bytes, r(1, 64), r(1, 77))
+    check("ladiff_linear_cross_attention_workspace_bytes", lib.ladiff_linear_cross_attention_workspace_bytes, r(1, 300), r(1, 8), r(1, 77))
+
+
+def test_reverse_workspace_query_is_monotonic_in_steps(lib):
+    """The step axis of ladiff_reverse_workspace_bytes over EVERY n up to 1100 at a few batches (test_workspace_queries_are_monotonic has
+    n in {1, 5, 50, 64, 65, 1000} at every batch).  The hoisted cross-attention table is held for one window of steps (csrc/api.hip reverse_window).  A schedule longer than 64
+    steps without a divisor that is a multiple of 10 used to keep ALL its steps resident, so 65 steps asked for more than 1000:
+    ladiff_reverse_workspace_bytes(300, 1, 65, 1) = 897,876,224 bytes against 783,413,504.  Now no window exceeds 64 steps and the carve
+    reserves min(n, 64) steps of table whatever the window, so every term of the query is non-decreasing in n."""
+    r = lambda lo, hi: list(range(lo, hi + 1))
+    for n_text in (1, 4):
+        _check_monotonic("ladiff_reverse_workspace_bytes", lambda B, T, n: lib.ladiff_reverse_workspace_bytes(B, T, n, n_text), [1, 7, 128, 300],
+                         [1, 5, 8], r(1, 1100))
+
+
+def test_graphed_decode_refuses_on_the_host_like_the_ragged_one(lib):
+    """ladiff_vae_decode_graphed checks shape, then the documented workspace query, before it captures or touches anything (as
+    ladiff_vae_decode_ragged does): host code only, so the pointers here are never followed."""
+    import ctypes
+    n = lib.ladiff_decoder_num_params()
+    w = (ctypes.c_void_p * n)(*[0x1000] * n)                  # a table of non-null weight pointers (copied, not followed)
+    g = ctypes.c_void_p()
+    assert lib.ladiff_decoder_graph_create(ctypes.byref(g)) == 0 and g.value
+    fake = ctypes.c_void_p(0x1000)
+    B, F, T, C = 4, 101, 5, 263
+    q = lib.ladiff_decoder_workspace_bytes(B, F, T, C)
+
+    def call(F, T, C, ws_bytes):
+        return lib.ladiff_vae_decode_graphed(g, w, None, 0, fake, fake, fake, fake, B * F, B, F, T, C, fake, fake, ws_bytes, fake)
+    assert call(F, T, C, q - 4) == -3                         # LADIFF_ERR_WORKSPACE
+    assert call(0, T, C, q) == -2 and call(F, 0, C, q) == -2 and call(F, T, 0, q) == -2 and call(225, T, C, q) == -2      # LADIFF_ERR_SHAPE
+    assert call(0, T, C, 0) == -2                             # shape first, as in the ragged entry
+
+
 def test_block_plan_of_the_pipeline_loop(lib):
     """Host arithmetic of the pipeline loop's block plan (ladiff_reverse_plan): padded 32-row blocks hold both guidance branches
     of 3 prompts, the length-aware 16-row packing one branch of as many prompts as fit with only their valid latent rows."""
