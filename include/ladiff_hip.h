@@ -466,6 +466,39 @@ LADIFF_API int ladiff_t2m_text_encode(const float* const* w, const float* word_e
 LADIFF_API int ladiff_feats2joints(const float* feats, const float* mean, const float* std, int B, int F, int C, int njoints,
                         float* joints, ladiff_stream_t stream);
 
+/* ------------------------------------------------------------------ joint-space metrics (csrc/joint_metrics.hip)
+ * The reference's ComputeMetrics ("TemosMetric": APE / AVE, models/metrics/compute.py:102-196) and MRMetrics (MPJPE / PA-MPJPE /
+ * ACCEL, models/metrics/mr.py:73-96) on joints_rst / joints_ref [B,F,J,3] as ladiff_feats2joints leaves them (call sites
+ * ladiff.py:1443-1445, :1464-1466), J = 21 or 22, 1 <= F <= LADIFF_MAX_FRAMES.  Each entry enqueues two launches and neither
+ * synchronises nor allocates: one workgroup per sequence writes that sequence's sums to seq_rows[b][:] (fp32; the arithmetic inside is
+ * fp64), then one workgroup adds the rows to acc[:] in fp64 in the order b = 0 .. B-1 (acc is caller-owned state: zero it to reset).  No
+ * floating-point atomics: acc's bits are reproducible, and one call on B sequences leaves the bits that calls on its consecutive parts
+ * leave.  No workspace.  h_lengths is the HOST copy of the lengths; LADIFF_ERR_SHAPE (nothing enqueued) for J outside {21, 22}, F outside
+ * [1, LADIFF_MAX_FRAMES], a length outside [1, F], a part index outside the skeleton or a misaligned pointer (4 bytes; acc 8).  B == 0
+ * does nothing.
+ *
+ * ladiff_joint_ape_ave: ComputeMetrics.transform = Rifke.forward (transforms/joints2jfeats/rifke.py:27-91, tools.py:14-55) and the
+ *   re-integration of compute.py:133-196 on both tensors - floor (soft minimum over ALL F frames of the padded tensor), root height,
+ *   trajectory and its differences, forward direction, its angle, the angle differences' prefix sum, local poses rotated back, the
+ *   local velocity rotated and prefix-summed, division by `factor` (compute.py:181-191: 1000 * 0.75 / 480 for humanml3d, 1000 for mmm,
+ *   1 without force_in_meter) - then over the frames < lengths[b] (device int32 [B]) the L2 sums and the variance(x, T) terms
+ *   (utils.py:8-16; a length of 1 divides by zero as the reference does).  seq_rows [B][W], acc [W], W = 4 + 2 (J - 1) + 2 J:
+ *   APE_root, APE_traj, APE_pose[J-1], APE_joints[J], AVE_root, AVE_traj, AVE_pose[J-1], AVE_joints[J].
+ *   h_part_idx[8] (host) = positions of LS, RS, LH, RH, LMrot, RMrot, LF, RF in the joint-name list (utils/joints.py:1-48).  As in the
+ *   reference the four foot joints index the full skeleton, while hips and shoulders index the poses after the root joint has been
+ *   removed (rifke.py:43, :55): joint (index + 1) of the input.
+ * ladiff_joint_mr: per frame, over EVERY one of the F frames (mr.py:92-96 passes the padded sequence whole): MPJPE root-aligned with
+ *   the target.x != -2 joint mask (utils.py:347-369), PA-MPJPE (utils.py:267-318, :389-406: means removed, K = X1 X2^T, its SVD with
+ *   the det-sign fix, scale, translation, mean joint error), ACCEL (utils.py:372-386: second differences, frames 0 .. F-3; nothing
+ *   when F < 3).  seq_rows [B][3], acc [3]: MPJPE, PAMPJPE, ACCEL.  F == 2 and F == 3: the reference takes a tensor whose
+ *   first dimension is 2 or 3 as transposed already (utils.py:274-278) and aligns each frame as 3 points (its x, y, z columns) in J
+ *   dimensions; PAMPJPE follows it there. */
+LADIFF_API int ladiff_joint_ape_ave(const float* joints_rst, const float* joints_ref, const int32_t* lengths, const int32_t* h_lengths,
+                         int B, int F, int J, const int32_t* h_part_idx, float factor, float* seq_rows, double* acc,
+                         ladiff_stream_t stream);
+LADIFF_API int ladiff_joint_mr(const float* joints_rst, const float* joints_ref, const int32_t* h_lengths, int B, int F, int J,
+                    float* seq_rows, double* acc, ladiff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ from .text_encoder import MldTextEncoder                # noqa: F401
 from .evaluators import (MovementConvEncoder, MotionEncoderBiGRUCo, TextEncoderBiGRUCo,   # noqa: F401
                          TM2TMetrics, MMMetrics)
 from .evaluation import evaluate, get_metric_statistics   # noqa: F401
+from .joint_metrics import ComputeMetrics, MRMetrics, TemosMetric   # noqa: F401
 
 __all__ = ["LADiffDenoiser", "LADiffVae", "LADIFF", "DDIMScheduler", "DDPMScheduler", "instantiate_from_config", "Feats2Joints", "MldTextEncoder", "MovementConvEncoder", "MotionEncoderBiGRUCo", "TextEncoderBiGRUCo",
-           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics"]
+           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics"]

@@ -894,6 +894,43 @@ int ladiff_feats2joints(const float* feats, const float* mean, const float* std,
     return launch_feats2joints(feats, mean, std, B, F, C, njoints, joints, S(stream));
 }
 
+// ------------------------------------------------------------------ joint-space metrics (csrc/joint_metrics.hip)
+namespace {
+// what both entries check on the host before anything is launched
+int joint_metrics_check(const void* rst, const void* ref, const int32_t* h_lengths, int B, int F, int J, const void* seq_rows, const void* acc) {
+    if (J != 21 && J != 22) return LADIFF_ERR_SHAPE;
+    if (F < 1 || F > LADIFF_MAX_FRAMES) return LADIFF_ERR_SHAPE;
+    for (int b = 0; b < B; ++b)
+        if (h_lengths[b] < 1 || h_lengths[b] > F) return LADIFF_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(rst) & 3) || (reinterpret_cast<uintptr_t>(ref) & 3) || (reinterpret_cast<uintptr_t>(seq_rows) & 3) ||
+        (reinterpret_cast<uintptr_t>(acc) & 7))
+        return LADIFF_ERR_SHAPE;
+    return 0;
+}
+}  // namespace
+
+int ladiff_joint_ape_ave(const float* joints_rst, const float* joints_ref, const int32_t* lengths, const int32_t* h_lengths, int B, int F,
+                         int J, const int32_t* h_part_idx, float factor, float* seq_rows, double* acc, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(B >= 0);
+    if (B == 0) return 0;
+    LADIFF_CHECK_ARG(joints_rst && joints_ref && lengths && h_lengths && h_part_idx && seq_rows && acc && factor > 0.f);
+    LADIFF_TRY(joint_metrics_check(joints_rst, joints_ref, h_lengths, B, F, J, seq_rows, acc));
+    if (reinterpret_cast<uintptr_t>(lengths) & 3) return LADIFF_ERR_SHAPE;
+    // LS, RS, LH, RH index the poses WITHOUT the root joint (J - 1 of them), the four foot joints the full skeleton
+    for (int i = 0; i < 8; ++i)
+        if (h_part_idx[i] < 0 || h_part_idx[i] >= (i < 4 ? J - 1 : J)) return LADIFF_ERR_SHAPE;
+    return launch_joint_ape_ave(joints_rst, joints_ref, lengths, B, F, J, h_part_idx, factor, seq_rows, acc, S(stream));
+}
+
+int ladiff_joint_mr(const float* joints_rst, const float* joints_ref, const int32_t* h_lengths, int B, int F, int J, float* seq_rows,
+                    double* acc, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(B >= 0);
+    if (B == 0) return 0;
+    LADIFF_CHECK_ARG(joints_rst && joints_ref && h_lengths && seq_rows && acc);
+    LADIFF_TRY(joint_metrics_check(joints_rst, joints_ref, h_lengths, B, F, J, seq_rows, acc));
+    return launch_joint_mr(joints_rst, joints_ref, B, F, J, seq_rows, acc, S(stream));
+}
+
 // ------------------------------------------------------------------ LA-VAE decoder
 size_t ladiff_decoder_workspace_bytes(int B, int F, int T, int C) {
     (void)C;

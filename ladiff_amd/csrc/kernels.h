@@ -81,6 +81,11 @@ int launch_decoder_cross_apply(const float* x, const float* bo, const float* g2,
 int launch_feats2joints(const float* feats, const float* mean, const float* stdv, int B, int F, int C, int J, float* joints,
                         hipStream_t s);
 
+// joint_metrics.hip: one row of sums per sequence, then the rows added to acc in fp64 in sequence order
+int launch_joint_ape_ave(const float* rst, const float* ref, const int32_t* lengths, int B, int F, int J, const int32_t* part_idx,
+                         float factor, float* seq_rows, double* acc, hipStream_t s);
+int launch_joint_mr(const float* rst, const float* ref, int B, int F, int J, float* seq_rows, double* acc, hipStream_t s);
+
 // attention.hip
 int launch_denoiser_self_attention(const float* qkv, const float* text_kv, const float* tables, int kv_off,
                                    int step_stride, const int32_t* d_step, const int32_t* counts, int Bs, int b_off,

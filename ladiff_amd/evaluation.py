@@ -15,7 +15,7 @@ def get_metric_statistics(values, replication_times):
     return values.mean(axis=0), 1.96 * values.std(axis=0) / np.sqrt(replication_times)
 
 
-def evaluate(model, tm2t_batches, mm_batches, replication_times=1, metrics=None):
+def evaluate(model, tm2t_batches, mm_batches, replication_times=1, metrics=None, joint_metrics=None):
     """Run the protocol on `model` (a `LADIFF` with evaluators set, or anything with its `t2m_eval(batch)` / `mm_eval(batch)`).
 
     Per replication, in the reference's order: every batch of `tm2t_batches` through `t2m_eval` into `TM2TMetrics.update(lat_t, lat_rm,
@@ -23,20 +23,30 @@ def evaluate(model, tm2t_batches, mm_batches, replication_times=1, metrics=None)
     `mm_eval`) through `mm_eval` into `MMMetrics.update(lat_rm, lengths)`, `compute()`; the two dicts merged.  Both iterables are walked
     once per replication (lists, DataLoaders; not one-shot generators).  `metrics` = (TM2TMetrics, MMMetrics) objects to use, reset
     before every replication like the reference's per-epoch reset; default-constructed when None.  `mm_batches` None or empty: no
-    multimodality pass.
+    multimodality pass.  `joint_metrics` = an iterable of joint-space metric objects (`ComputeMetrics` / `TemosMetric`, `MRMetrics`:
+    the other classes of the reference's `METRIC.TYPE`), each reset per replication, updated in the TM2T pass with `(joints_rst,
+    joints_ref, batch["length"])` (`ladiff.py:1443-1445, 1464-1466`) and its `compute()` merged into the replication's values; None:
+    none.
 
     Returns (stats, per_replication): stats[name] = (mean, conf_interval) from `get_metric_statistics`, per_replication[name] = the list
     of `replication_times` values."""
     if replication_times < 1:
         raise ValueError("replication_times must be >= 1")
     tm2t, mm = metrics if metrics is not None else (TM2TMetrics(), MMMetrics())
+    joint_metrics = list(joint_metrics) if joint_metrics is not None else []
     all_metrics = {}
     for _ in range(replication_times):
         tm2t.reset()
+        for jm in joint_metrics:
+            jm.reset()
         for batch in tm2t_batches:
             rs = model.t2m_eval(batch)
             tm2t.update(rs["lat_t"], rs["lat_rm"], rs["lat_m"], batch["length"])
+            for jm in joint_metrics:
+                jm.update(rs["joints_rst"], rs["joints_ref"], batch["length"])
         values = dict(tm2t.compute(sanity_flag=False))
+        for jm in joint_metrics:
+            values.update(jm.compute(sanity_flag=False))
         if mm_batches is not None and mm is not None:
             mm.reset()
             seen = False
