@@ -378,29 +378,6 @@ int ladiff_sampler_destroy(void* sampler) {
 
 }  // extern "C"
 
-// Block plan of the pipeline loop for one call (host only).  loop_mode: 1 = pick by the cost model, 2 / 3 = force 16- / 32-row blocks.
-static void choose_plan(int B, int T, const int32_t* h_counts, bool masked, int loop_mode, bool f16x3, std::vector<unsigned char>& plan,
-                        int* plan_mr, int* plan_nb, bool cfg = true) {
-    int mr16 = 1, nb16 = 0, mr32 = 2, nb32 = 0;
-    std::vector<unsigned char> p16, p32;
-    if (!cfg) {             // no guidance: one-branch 16-row blocks only (the caller made sure the counts are on the host, or absent)
-        sys_pack_blocks(B, T, 1, h_counts, masked, false, plan, plan_mr, plan_nb);
-        return;
-    }
-    sys_pack_blocks(B, T, 2, h_counts, masked, true, p32, &mr32, &nb32);
-    int want = loop_mode == 2 ? 1 : (loop_mode == 3 ? 2 : 0);
-    if (want != 2) sys_pack_blocks(B, T, 1, h_counts, masked, true, p16, &mr16, &nb16);
-    if (want == 0) {
-        // measured (scripts/try_pipeline.py uniform, 1 ... 128 prompts, final build of round 2): the busiest stage's time per block
-        // and one block's unloaded trip through the 59 stages, in us, for 16- / 32-row blocks
-        const double c16 = f16x3 ? 2.45 : 5.05, c32 = f16x3 ? 5.3 : 12.1, lat16 = f16x3 ? 172.0 : 310.0, lat32 = f16x3 ? 282.0 : 525.0;
-        const double e16 = mr16 == 1 ? std::max(lat16, nb16 * c16) : 1e30, e32 = std::max(lat32, nb32 * c32);
-        want = e16 < e32 ? 1 : 2;
-    }
-    if (want == 1 && mr16 == 1) { plan.swap(p16); *plan_mr = 1; *plan_nb = nb16; }
-    else { plan.swap(p32); *plan_mr = 2; *plan_nb = nb32; }
-}
-
 extern "C" {
 
 int ladiff_reverse_plan(int B, int T, const int32_t* h_counts, int masked, int loop_mode, int f16x3, int cfg, int* rows_per_block, int* n_blocks) {

@@ -4,6 +4,7 @@
 #include "gemm.h"
 #include "gemm_kr.h"
 #include "kernels.h"
+#include "systolic_plan.h"
 #include "weights.h"
 
 namespace ladiff {
@@ -68,21 +69,18 @@ int vae_encode(const EncoderW& w, const EncoderW* w_split, const float* features
                const int32_t* counts, const float* eps, int B, int F, int T, int C, float* mu, float* sd, float* latent, float* ws,
                size_t ws_floats, hipStream_t s);
 
-// systolic.hip: the guided denoiser loop as one persistent weight-stationary pipeline (both arithmetic modes)
+// systolic.hip: the guided denoiser loop as one persistent weight-stationary pipeline (both arithmetic modes); its host planner
+// (workspace carve, block packing, stage table, choose_plan) is systolic_plan.hip, declared in systolic_plan.h
 #ifdef LADIFF_STAMPS
 extern unsigned long long* g_sys_stamps;
 extern int g_sys_probe;
 #endif
-size_t sys_ws_floats(int B, int T);
 bool sys_supported(int B, int T, int cfg, bool split);
 extern std::atomic<int> g_waves16;
 extern std::atomic<int> g_handoff;
 int sys_reset_status(float* ws, hipStream_t s);
 extern std::atomic<int> g_xcd_local;
-void sys_pack_blocks(int B, int T, int want_mr, const int32_t* h_counts, bool masked, bool cfg, std::vector<unsigned char>& out, int* mr, int* nb);
-int sys_build_stages(const DenoiserW& W, const DenoiserW& WS, float* ws, int MR, int NB, std::vector<unsigned char>& host);
-size_t sys_blocks_offset_floats(int MR, int NB);
-size_t sys_status_offset_floats(int B, int T);
+int sys_build_stages(const DenoiserW& W, const DenoiserW& WS, float* ws, int MR, int NB, std::vector<unsigned char>& host);   // probes the device, then the planner's
 int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab,
                          const float* coef, const float* noise, float* lat, const int32_t* counts, float gscale, int B, int T,
                          int step_lo, int n, int fp32, int MR, int NB, hipStream_t s, int cfg = 1, int fault_wg = -1,

@@ -42,6 +42,10 @@
 // fp16 halves (bf16 halves in the -DLADIFF_SPLIT_BF16 build), hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16 (_bf16), fp32
 // accumulation and fp32 everything else; AR = 1 is the fp32 mode.  Only the summation order of the split products differs from the
 // launch-per-stage loop (8 hidden slices instead of 4 K-slices).
+//
+// This file: the device code (hand-off protocols, the eight roles, the kernel), the XCD probe and the launch.  The plan they run - the
+// constants, Stage, BlockDesc, the workspace carve, the block packing, the stage table and its placement - is host arithmetic with no HIP
+// call: systolic_plan.h / systolic_plan.hip, built and tested without a GPU (tests/planner_check.cpp).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -53,7 +57,7 @@
 
 namespace ladiff {
 
-std::atomic<int> g_stage_plan{0};   // measurement switch: ladiff_debug_set_stage_plan (red_plan below)
+std::atomic<int> g_stage_plan{0};   // measurement switch: ladiff_debug_set_stage_plan (red_plan, systolic_plan.h)
 std::atomic<int> g_poll_pause{0};   // measurement switch: ladiff_debug_set_poll_pause (mask | len << 8)
 std::atomic<int> g_stage_delay{-1}; // ladiff_debug_set_stage_delay (mask | len << 8); -1: by block count (launch_systolic_loop)
 std::atomic<int> g_look_ahead_from{-1}, g_small_upto{-1};   // ladiff_debug_set_loop_thresholds (-1: the built-in block counts)
@@ -71,55 +75,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #endif
 constexpr int PF1 = LADIFF_PF1;           // fragment fetch distance of the one-column-tile products (tile_mma.h, mma): LIN / FFN first product, QKV's third tile
 constexpr int PF2 = LADIFF_PF2;           // ... of the two-tile products of the eight-wave roles
-constexpr int NSLICE = 8;                 // hidden slices of the two MLPs (128 columns each)
-constexpr int HS = FF / NSLICE;           // 128
-constexpr int NRED = 3;                   // workgroups per layer of each of the two reduce stages (how they share the work: red_parts())
-constexpr int NTAIL = 4;                  // tail workgroups (block b belongs to tail b % NTAIL)
-constexpr int FLAG_SLOTS = 16;
-// The eight partial planes of a layer's two K-split matrices (LIN -> RED2, FFN -> STYL) are RINGS of PRING block slots, not NB:
-// with a buffer set per layer (sys_layout) they would otherwise be most of a working set larger than the 256 MiB memory-side
-// cache.  A producer may therefore run at most PRING blocks ahead of its consumer: every PRING / 2 blocks it waits for the
-// consumer's flag of the block PRING / 2 back (MlpRole::backpressure; the stages visit their blocks in order).  The slot of
-// block b of local step s is (s NB + b) % PRING: blocks are counted THROUGH the steps, so that the reuse distance is PRING
-// blocks at the wrap from one step to the next as well.
-constexpr int PRING = 16;
-// What the one-bit tag of a ring slot needs from these constants (the invariant in the header of this file).  A producer looks back
-// every PRING / 2 blocks, at the consumer's block PRING / 2 back and - where the consumer is MAX_BP_BLOCKS groups on alternating
-// blocks - at the blocks just before it: the look-back must be a whole number of blocks, and every block it looks at must lie
-// inside the ring's previous half, so that "the consumer has finished them" covers exactly the slots the next PRING / 2 blocks overwrite.
-constexpr int MAX_BP_BLOCKS = 2;            // consecutive blocks that make "all consumers" (Stage::bp_blocks <= this: red_plan's styl_groups)
-static_assert(PRING >= 2 && PRING % 2 == 0, "the back-pressure look-back is PRING / 2 blocks");
-static_assert(MAX_BP_BLOCKS <= PRING / 2, "every block a producer looks back at must be in the half ring it is about to leave alone");
-constexpr int SMALL_LAUNCH_BLOCKS = 60;     // launches up to this many blocks: LIN / FFN rest after every block (launch_systolic_loop)
 constexpr int PACED_ROLES = 4;              // stage types (R::PAUSE_BIT) whose polling is paced (tag_loop): STYL
-constexpr int FLAG_STRIDE = 32;             // words between the flags of two producers: every flag on a 128-byte line of its own
-constexpr int SYS_LDS_BYTES = 100 * 1024;   // > 80 KiB: one workgroup per CU, so the <= 256 workgroups sit on distinct CUs
-constexpr int GROUPS_PER_LAYER = 7;
-enum Group : int { G_XIN = 0, G_ATT = 1, G_X1 = 2, G_PC = 3, G_X2 = 4, G_PE = 5, G_XO = 6 };
-enum Role : int { R_QKV = 0, R_OUT = 1, R_LIN = 2, R_RED2 = 3, R_FFN = 4, R_STYL = 5, R_SKIP = 6, R_TAIL = 7 };
-
-struct Stage {                            // one per workgroup
-    int role, layer, slice, act;
-    int wait_group, wait_n, out_group, out_slot;
-    int blk0, blkstride;                  // the blocks this workgroup visits: blk0, blk0 + blkstride, ...
-    // A flag with many consumer workgroups is REPLICATED, one 128-byte line per consumer: the producer raises out_rep flags (slots
-    // out_slot + i out_rep_stride) with one store instruction, a consumer polls wait_n slots from wait_slot0.  Sixty-four waves
-    // polling one line made every poll of that line slow - and those were the inputs of the two busiest stage types (LIN, FFN).
-    int wait_slot0, out_rep, out_rep_stride;
-    // XCD placement (sys_place_stages): workgroup i runs on XCD i % 8 and each XCD has an L2 of its own.  out_local = every reader
-    // of this stage's output (rows and flags) sits on the SAME XCD: the stage then stores plainly - the rows stay in that L2, the
-    // store is acknowledged by the L2 instead of the memory side (a hop of 0.5 us instead of 0.9 - 1.2 us,
-    // scripts/ubench_xcd_handoff.hip) - otherwise it writes through (sc1).  Loads are sc1 either way: they are served by the
-    // reader's L2 when the line is there.  xcd = the XCD the plan put this workgroup on (-1: not checked).
-    int out_local, xcd, pad0;
-    int bp_group, bp_slot0, bp_n, bp_blocks;   // LIN / FFN: the consumer's flags (group, first slot, count) and how many consecutive blocks make "all consumers"
-    const float *w0, *w1;                 // S-format matrices
-    const float *b0, *b1;                 // biases
-    const float *g, *be;                  // LayerNorm gamma / beta
-    const float *in0, *in1, *in2;         // block-layout activations: [NB][RT][256] (partials: [8][NB][RT][256])
-    float* out;
-    const float* bp_buf;                  // LIN / FFN, tagged hand-off: the consumer's OUTPUT rows (their tags are the ring's back-pressure)
-};
 
 // The workgroup's Stage arrives as a few wide scalar loads (s_load_dwordx16): sixteen-register tuples.  The register allocator keeps a
 // tuple whole - the roles' buffer resources were even built IN one (its dead words reused for the resource's constant words) - and the
@@ -138,43 +94,6 @@ __device__ __forceinline__ void own_stage(Stage& st) {
     own_sgpr(st.bp_group); own_sgpr(st.bp_slot0); own_sgpr(st.bp_n); own_sgpr(st.bp_blocks);
     own_sgpr(st.w0); own_sgpr(st.w1); own_sgpr(st.b0); own_sgpr(st.b1); own_sgpr(st.g); own_sgpr(st.be);
     own_sgpr(st.in0); own_sgpr(st.in1); own_sgpr(st.in2); own_sgpr(st.out); own_sgpr(st.bp_buf);
-}
-
-// Geometry of one block, built on the host (sys_pack_blocks).  32-row tiles: both guidance branches of P prompts, T rows each
-// (the latent count masks keys).  16-row tiles: ONE guidance branch of as many prompts as fit with only their count[b] valid
-// latent rows (length-aware: padded latent rows never influence valid ones - they are masked as keys, every other op is
-// per row, and ladiff.py:559-566 zeroes them at the end - so they are not computed at all).
-struct BlockDesc {
-    int nrows, nsb, pad0, pad1;
-    int b2[16];                           // per sample-branch sx: text-cache row (-1: absent)
-    // attention stage, per tile row: sx | first tile row of sx << 8 | valid latent keys << 16 (0xff: counts[] at run time); the
-    // row's cross-attention / counts row (-1: padding)
-    int row_pk[32], row_b2[32];
-    int row_lat[32], row_t[32];           // latents row (prompt * T + t, -1: padding) and latent index of a tile row
-    // reduce stages: part q of NRED handles slot k = wave + 4 i -> tile row | latent index << 8 | latent count << 16 (0xff: run
-    // time), -1: no row; and the row's cross-attention table row.  The parts cover ALL rows of the tile: a row past nrows
-    // (PART_PAD | row) is stored as zeros - under the tagged hand-off every row of a tile carries the step's parity, so that a
-    // consumer checks whole tiles and needs no geometry.
-    int part_pk[3][12], part_b2[3][12];
-    // tail: (prompt, latent) pair k = wave + 4 i -> latents row (-1: none), latent index, tile row of the conditional branch.
-    // A slot without a pair zeroes two padding rows instead: row pair_pad of the unconditional block and row pair_rc of the
-    // conditional one (-1: nothing left to pad)
-    int pair_lat[16], pair_t[16], pair_rc[16], pair_pad[16];
-};
-constexpr int PART_PAD = 0x40000000;
-static_assert(NRED == 3, "BlockDesc::part_pk");
-// How the reduce workgroups of a layer share a block's rows.  32-row blocks: NRED row parts each (<= 11 rows, 3 per wave).
-// 16-row blocks: a part can take 8 rows (2 per wave), so RED2 needs only two workgroups and the freed one goes to STYL, the
-// busiest stage of that plan: two GROUPS of two parts, group g visiting the blocks b = g (mod 2) - it sees every other block.
-struct RedPlan { int red2_parts, styl_parts, styl_groups, out_groups; };
-// how a layer's workgroups that hold no MLP slice are dealt (16-row blocks): variant 0 = one OUT workgroup, STYL as two groups on
-// alternating blocks x two row parts; variant 1 = OUT as two groups on alternating blocks, STYL as one group x two row parts
-constexpr RedPlan PLAN32{NRED, NRED, 1, 1}, PLAN16{2, 2, 2, 1}, PLAN16_OUT2{2, 2, 1, 2};
-static_assert(PLAN32.styl_groups <= MAX_BP_BLOCKS && PLAN16.styl_groups <= MAX_BP_BLOCKS && PLAN16_OUT2.styl_groups <= MAX_BP_BLOCKS,
-              "a ring's producer looks back at styl_groups consecutive blocks (Stage::bp_blocks): see PRING");
-inline RedPlan red_plan(int MR) {
-    if (MR != 1) return PLAN32;
-    return g_stage_plan.load() == 1 ? PLAN16_OUT2 : PLAN16;
 }
 
 struct SysArgs {
@@ -2334,56 +2253,8 @@ __global__ __launch_bounds__(256 * WS, 1) void systolic_loop_kernel(const SysArg
 unsigned long long* g_sys_stamps = nullptr;
 int g_sys_probe = 0;                                                   // diagnostic twin build: SysArgs::probe
 #endif
-namespace {
-struct SysLayout {
-    size_t blk, ring;             // floats of one [NB][RT][256] buffer / of one [PRING][RT][256] partial plane
-    size_t off_stages, off_blocks, off_flags, off_status, off_xin0, off_xs, off_xo, off_att, off_x1, off_x2, off_pc, off_pe, total;
-    int nwg, NB, split;
-};
 constexpr int NWG = NL * (4 + 1 + NSLICE + NRED + NSLICE + NRED) + 2 * NSKIP + NTAIL;     // the largest plan
-int plan_nwg(int MR) {
-    const RedPlan rp = red_plan(MR);
-    return NL * (4 + rp.out_groups + NSLICE + rp.red2_parts + NSLICE + rp.styl_parts * rp.styl_groups) + 2 * NSKIP + NTAIL;
-}
-// 32-row tiles: P prompts per block, both guidance branches, T rows each
-int prompts_per_block32(int T) { int P = 32 / (2 * T); return P > 7 ? 7 : (P < 1 ? 1 : P); }   // QKV parks <= 14 text K|V slots
-int nb32(int B, int T) { const int P = prompts_per_block32(T); return (B + P - 1) / P; }
-// 16-row tiles, worst case of the packing (every prompt with all T rows): floor(16 / T) prompts (<= 8) per branch block
-int nb16_max(int B, int T) { int P = 16 / T; P = P > 8 ? 8 : (P < 1 ? 1 : P); return 2 * ((B + P - 1) / P); }
-
-SysLayout sys_layout(int MR, int NB) {
-    SysLayout L;
-    const int RT = 16 * MR;
-    L.split = MR == 1 ? 1 : 0;
-    L.NB = NB;
-    L.nwg = plan_nwg(MR);
-    L.blk = (size_t)NB * RT * D;
-    size_t off = 0;
-    auto take = [&](size_t floats) { const size_t o = off; off += (floats + 63) / 64 * 64; return o; };
-    L.off_stages = take((size_t)256 * sizeof(Stage) / sizeof(float));
-    L.off_status = take(64);      // before everything sized by the block geometry: ladiff_reverse_status reads it at a fixed offset
-    L.off_blocks = take((size_t)NB * sizeof(BlockDesc) / sizeof(float));
-    L.off_flags = take((size_t)NL * GROUPS_PER_LAYER * NB * FLAG_SLOTS * FLAG_STRIDE);
-    L.off_xin0 = take(L.blk);
-    L.off_xs = take(NSKIP * L.blk);
-    L.off_xo = take(NL * L.blk);
-    // one set per LAYER: a buffer is then written by the workgroups of one stage group only - on one XCD when the group stores
-    // plainly (Stage::out_local), so that no line is ever dirty in two L2s
-    L.off_att = take(NL * L.blk);
-    L.off_x1 = take(NL * L.blk);
-    L.off_x2 = take(NL * L.blk);
-    L.ring = (size_t)PRING * RT * D;                                  // floats of one partial plane: a ring of PRING block slots
-    L.off_pc = take((size_t)NL * NSLICE * L.ring);
-    L.off_pe = take((size_t)NL * NSLICE * L.ring);
-    L.total = off;
-    return L;
-}
-}  // namespace
-
-size_t sys_ws_floats(int B, int T) {
-    const size_t a = sys_layout(1, nb16_max(B, T)).total, b = sys_layout(2, nb32(B, T)).total;
-    return a > b ? a : b;
-}
+static_assert(D == LADIFF_LATENT_DIM && H == LADIFF_NUM_HEADS, "systolic_plan.hip takes both from the ABI header");
 
 bool sys_supported(int B, int T, int cfg, bool split) {
     (void)split; (void)cfg;       // both arithmetic modes and both guidance settings have a pipeline form
@@ -2394,114 +2265,8 @@ bool sys_supported(int B, int T, int cfg, bool split) {
     return cus >= NWG;            // every stage needs a CU of its own, all resident at once
 }
 
-// Block geometry for this call (host).  h_counts = the latent counts on the HOST (or NULL); masked = the call has device counts.
-//   MR 2: blocks of P consecutive prompts, both branches, T rows per prompt; the count only masks keys (cnt = -1 when the host
-//         does not know it: the kernel reads counts[] itself).
-//   MR 1: LENGTH-AWARE packing - prompts sorted by latent count, a block = one guidance branch of as many prompts as fit in 16
-//         rows with ONLY their count[b] valid rows (padded latent rows are never computed); needs the counts on the host.
-// Returns the plan: `blocks`, and in `mr` the tile size actually planned (MR 1 falls back to 2 when the counts are device-only).
-// cfg = false (no classifier-free guidance, ladiff.py:472-490: the network sees the B latents once): 16-row blocks of ONE branch, no
-// partner block - the tail treats a block as a unit whose "conditional" row is the row itself (guidance then adds g * 0 exactly).
-void sys_pack_blocks(int B, int T, int want_mr, const int32_t* h_counts, bool masked, bool cfg, std::vector<unsigned char>& out, int* mr, int* nb) {
-    std::vector<BlockDesc> blocks;
-    auto count_of = [&](int b) { int c = (masked && h_counts) ? h_counts[b] : T; return c > T ? T : (c < 1 ? 1 : c); };
-    int MR = want_mr;
-    if (!cfg) MR = 1;                                                  // the caller checked sys_plan_possible()
-    if (MR == 1 && masked && h_counts == nullptr && cfg) MR = 2;
-    auto fresh = [] { BlockDesc d; std::memset(&d, 0, sizeof(d)); for (int i = 0; i < 16; ++i) d.b2[i] = -1;
-                      for (int r = 0; r < 32; ++r) { d.row_b2[r] = -1; d.row_lat[r] = -1; } return d; };
-    // derived tables: the reduce parts' slots (the live rows split evenly over NRED parts) and the tail's (prompt, latent) pairs
-    auto finish = [&](BlockDesc& d, const int* row_cnt, int npairs, int rc_off) {
-        const int nparts = red_plan(MR).red2_parts;               // RED2 and STYL split a block's rows the same way
-        const int RT = 16 * MR, per = (RT + nparts - 1) / nparts; // all rows of the tile, padding included (stored as zeros)
-        for (int part = 0; part < NRED; ++part) {
-            const int lo = part * per < RT ? part * per : RT, hi = lo + per < RT ? lo + per : RT;
-            for (int k = 0; k < 12; ++k) {
-                const int r = lo + k;
-                d.part_pk[part][k] = -1; d.part_b2[part][k] = -1;
-                if (part < nparts && r < hi) {
-                    if (r < d.nrows) {
-                        d.part_pk[part][k] = r | d.row_t[r] << 8 | (row_cnt[r] < 0 ? 0xff : row_cnt[r]) << 16;
-                        d.part_b2[part][k] = d.row_b2[r];
-                    } else {
-                        d.part_pk[part][k] = PART_PAD | r;
-                    }
-                }
-            }
-        }
-        // tail: pairs first; the slots behind them pad.  One-branch blocks (rc_off 0): slot q pads row q of both blocks of the unit;
-        // two-branch blocks: the pad slots share the rows from nrows up, two each (both in the unit's one block)
-        for (int q = 0; q < 16; ++q) {
-            d.pair_lat[q] = -1; d.pair_t[q] = 0; d.pair_rc[q] = -1; d.pair_pad[q] = -1;
-            if (q < npairs) { d.pair_lat[q] = d.row_lat[q]; d.pair_t[q] = d.row_t[q]; d.pair_rc[q] = q + rc_off; }
-            else if (rc_off == 0) { if (q < RT) { d.pair_pad[q] = q; d.pair_rc[q] = q; } }
-            else {
-                const int r = d.nrows + 2 * (q - npairs);
-                if (r < RT) d.pair_pad[q] = r;
-                if (r + 1 < RT) d.pair_rc[q] = r + 1;
-            }
-        }
-    };
-    if (MR == 2) {
-        const int P = prompts_per_block32(T);
-        for (int p0 = 0; p0 < B; p0 += P) {
-            const int Pb = B - p0 < P ? B - p0 : P;
-            BlockDesc d = fresh();
-            d.nsb = 2 * Pb; d.nrows = 2 * Pb * T;
-            int row_cnt[32];
-            for (int br = 0; br < 2; ++br)
-                for (int pl = 0; pl < Pb; ++pl) {
-                    const int sx = br * Pb + pl, prompt = p0 + pl;
-                    const int cnt = masked ? (h_counts ? count_of(prompt) : -1) : T;
-                    d.b2[sx] = br * B + prompt;
-                    for (int t = 0; t < T; ++t) {
-                        const int r = sx * T + t;
-                        d.row_pk[r] = sx | (sx * T) << 8 | (cnt < 0 ? 0xff : cnt) << 16;
-                        d.row_t[r] = t; d.row_b2[r] = br * B + prompt; row_cnt[r] = cnt; d.row_lat[r] = prompt * T + t;
-                    }
-                }
-            finish(d, row_cnt, d.nrows / 2, d.nrows / 2);                // conditional row of a pair: nrows / 2 further
-            blocks.push_back(d);
-        }
-    } else {
-        std::vector<int> order(B);
-        for (int b = 0; b < B; ++b) order[b] = b;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return count_of(a) > count_of(b); });
-        size_t i = 0;
-        while (i < order.size()) {
-            std::vector<int> group;
-            int rows = 0;
-            while (i < order.size() && group.size() < 8 && rows + count_of(order[i]) <= 16) { rows += count_of(order[i]); group.push_back(order[i]); ++i; }
-            for (int br = 0; br < (cfg ? 2 : 1); ++br) {
-                BlockDesc d = fresh();
-                d.nsb = (int)group.size(); d.nrows = rows;
-                int r0 = 0, row_cnt[32];
-                for (int sx = 0; sx < (int)group.size(); ++sx) {
-                    const int prompt = group[sx], cnt = count_of(prompt);
-                    d.b2[sx] = br * B + prompt;
-                    for (int t = 0; t < cnt; ++t) {
-                        const int r = r0 + t;
-                        d.row_pk[r] = sx | r0 << 8 | cnt << 16;
-                        d.row_t[r] = t; d.row_b2[r] = br * B + prompt; row_cnt[r] = cnt; d.row_lat[r] = prompt * T + t;
-                    }
-                    r0 += cnt;
-                }
-                finish(d, row_cnt, rows, 0);                             // the conditional branch is the next block, same row
-                blocks.push_back(d);
-            }
-        }
-    }
-    out.resize(blocks.size() * sizeof(BlockDesc));
-    std::memcpy(out.data(), blocks.data(), out.size());
-    *mr = MR; *nb = (int)blocks.size();
-}
-
-// Builds the stage table (host) for this call's pointers.  `ws` = the systolic region of the reverse workspace.
-// ---- XCD placement.  The dispatcher hands workgroup i of a launch to XCD i % 8 (from wherever the previous launch
-// stopped; checked once per device by a probe launch of the same shape, and by every pipeline workgroup when it starts: status 3).  `st` comes in CHAIN order (the order a block
-// flows through the stages); the stages are dealt to the XCDs in that order, 32 (31) to each, so that a layer's hand-offs stay
-// inside one XCD's L2 and the chain crosses an XCD boundary only 7 times (+ the skip connections and the tail).  A stage whose
-// readers all sit on its own XCD stores plainly (Stage::out_local); everything else works as before (write-through).
+// ---- XCD placement (sys_place_stages, systolic_plan.hip) rests on the dispatcher handing workgroup i of a launch to XCD i % 8: checked
+// once per device by a probe launch of the pipeline's shape, here, and by every pipeline workgroup when it starts.
 std::atomic<int> g_xcd_local{1};  // measurement switch: ladiff_debug_set_xcd_local
 
 __global__ __launch_bounds__(512, 1) void xcd_probe_kernel(unsigned* xcc) {
@@ -2533,119 +2298,10 @@ static bool xcd_round_robin() {
     }
     return known[dev] == 1;
 }
-static void sys_place_stages(std::vector<Stage>& st) {
-    const int n = (int)st.size();
-    std::vector<Stage> placed(n);
-    int cnt[8] = {}, k = 0;
-    for (int j = 0; j < n; ++j) {
-        while (cnt[k] == (n - k + 7) / 8) ++k;                        // XCD k runs workgroups k, k + 8, ...
-        st[j].xcd = k;
-        placed[k + 8 * cnt[k]++] = st[j];
-    }
-    for (Stage& p : placed) {
-        bool local = true;
-        for (const Stage& c : placed) {
-            const bool reads = c.in0 == p.out || c.in1 == p.out || c.in2 == p.out;                       // its rows
-            const bool polls = c.wait_group == p.out_group || (c.bp_n > 0 && c.bp_group == p.out_group);  // its flags
-            if ((reads || polls) && c.xcd != p.xcd) local = false;
-        }
-        p.out_local = local ? 1 : 0;
-    }
-    st.swap(placed);
-}
 
+// The stage table for this call's pointers: the planner's, placed on the XCDs where the switch allows it and the probe found round robin.
 int sys_build_stages(const DenoiserW& W, const DenoiserW& WS, float* ws, int MR, int NB, std::vector<unsigned char>& host) {
-    // WS = the S-format weight table in f16x3 mode; in fp32 mode the caller passes the fp32 table twice
-    const SysLayout L = sys_layout(MR, NB);
-    const RedPlan rp = red_plan(MR);
-    std::vector<Stage> st;
-    float* xin0 = ws + L.off_xin0;
-    auto XO = [&](int l) { return ws + L.off_xo + (size_t)l * L.blk; };
-    auto XS = [&](int l) { return ws + L.off_xs + (size_t)(l - NSKIP - 1) * L.blk; };
-    auto G = [&](int l, int g) { return l * GROUPS_PER_LAYER + g; };
-    const bool x2_rep = rp.red2_parts * NSLICE <= FLAG_SLOTS;
-    for (int l = 0; l < NL; ++l) {
-        const DenLayerW& w = W.layer[l];
-        const DenLayerW& ws_ = WS.layer[l];
-        float* att = ws + L.off_att + (size_t)l * L.blk; float* x1 = ws + L.off_x1 + (size_t)l * L.blk; float* x2 = ws + L.off_x2 + (size_t)l * L.blk;
-        float* pc = ws + L.off_pc + (size_t)l * NSLICE * L.ring; float* pe = ws + L.off_pe + (size_t)l * NSLICE * L.ring;
-        const float* xin; int xg, xn;
-        if (l == 0) { xin = xin0; xg = G(0, G_XIN); xn = 1; }
-        else if (l <= NSKIP) { xin = XO(l - 1); xg = G(l - 1, G_XO); xn = rp.styl_parts; }
-        else { xin = XS(l); xg = G(l, G_XIN); xn = 2; }
-        if (l > NSKIP) {
-            const int i = l - NSKIP - 1;
-            for (int c = 0; c < 2; ++c) {
-                Stage s{};
-                s.role = R_SKIP; s.layer = l; s.slice = c; s.wait_group = G(l - 1, G_XO); s.wait_n = rp.styl_parts;
-                s.out_group = G(l, G_XIN); s.out_slot = c;
-                s.w0 = WS.skip[i].w; s.b0 = W.skip[i].b; s.in0 = XO(l - 1); s.in1 = XO(NL - 1 - l); s.out = XS(l);
-                st.push_back(s);
-            }
-        }
-        for (int h = 0; h < H; ++h) {
-            Stage s{};
-            s.role = R_QKV; s.layer = l; s.slice = h; s.wait_group = xg; s.wait_n = xn; s.out_group = G(l, G_ATT); s.out_slot = h;
-            s.w0 = ws_.sa_attn.in_w; s.b0 = w.sa_attn.in_b; s.in0 = xin; s.out = att;
-            st.push_back(s);
-        }
-        for (int g = 0; g < rp.out_groups; ++g) {                         // groups: workgroups of their own on alternating blocks
-            Stage s{};
-            s.role = R_OUT; s.layer = l; s.wait_group = G(l, G_ATT); s.wait_n = H; s.out_group = G(l, G_X1); s.out_slot = 0;
-            s.out_rep = NSLICE; s.out_rep_stride = 1;                     // one flag line per LIN workgroup
-            s.blk0 = g; s.blkstride = rp.out_groups;
-            s.w0 = ws_.sa_attn.out_w; s.b0 = w.sa_attn.out_b; s.g = w.sa_norm1.g; s.be = w.sa_norm1.b; s.in0 = att; s.in1 = xin; s.out = x1;
-            st.push_back(s);
-        }
-        for (int j = 0; j < NSLICE; ++j) {
-            Stage s{};
-            s.role = R_LIN; s.layer = l; s.slice = j; s.wait_group = G(l, G_X1); s.wait_n = 1; s.out_group = G(l, G_PC); s.out_slot = j;
-            s.wait_slot0 = j;
-            s.bp_group = G(l, G_X2); s.bp_slot0 = x2_rep ? j * rp.red2_parts : 0; s.bp_n = rp.red2_parts; s.bp_blocks = 1; s.bp_buf = x2;
-            s.w0 = ws_.sa_lin1.w; s.w1 = ws_.sa_lin2.w; s.b0 = w.sa_lin1.b; s.in0 = x1; s.out = pc;
-            st.push_back(s);
-        }
-        for (int q = 0; q < rp.red2_parts; ++q) {
-            Stage s{};
-            s.role = R_RED2; s.layer = l; s.slice = q; s.wait_group = G(l, G_PC); s.wait_n = NSLICE; s.out_group = G(l, G_X2); s.out_slot = q;
-            if (x2_rep) { s.out_rep = NSLICE; s.out_rep_stride = rp.red2_parts; }   // FFN workgroup j polls slots j parts + q
-            s.b0 = w.sa_lin2.b; s.g = w.sa_norm2.g; s.be = w.sa_norm2.b; s.in0 = pc; s.in1 = x1; s.out = x2;
-            st.push_back(s);
-        }
-        for (int j = 0; j < NSLICE; ++j) {
-            Stage s{};
-            s.role = R_FFN; s.layer = l; s.slice = j; s.wait_group = G(l, G_X2); s.wait_n = rp.red2_parts; s.out_group = G(l, G_PE); s.out_slot = j;
-            if (x2_rep) s.wait_slot0 = j * rp.red2_parts;
-            s.bp_group = G(l, G_XO); s.bp_slot0 = 0; s.bp_n = rp.styl_parts; s.bp_blocks = rp.styl_groups; s.bp_buf = XO(l);
-            s.w0 = ws_.ffn1.w; s.w1 = ws_.ffn2.w; s.b0 = w.ffn1.b; s.in0 = x2; s.out = pe;
-            st.push_back(s);
-        }
-        for (int g = 0; g < rp.styl_groups; ++g)
-            for (int q = 0; q < rp.styl_parts; ++q) {
-                Stage s{};
-                s.role = R_STYL; s.layer = l; s.slice = q; s.wait_group = G(l, G_PE); s.wait_n = NSLICE; s.out_group = G(l, G_XO); s.out_slot = q;
-                s.blk0 = g; s.blkstride = rp.styl_groups;
-                s.w0 = ws_.ffn_proj.out.w; s.b0 = w.ffn_proj.out.b; s.b1 = w.ffn2.b; s.g = w.ffn_proj.norm.g; s.be = w.ffn_proj.norm.b;
-                s.in0 = pe; s.in1 = x2; s.out = XO(l);
-                st.push_back(s);
-            }
-    }
-    for (int k = 0; k < NTAIL; ++k) {
-        Stage s{};
-        s.role = R_TAIL; s.layer = NL; s.slice = k; s.wait_group = G(NL - 1, G_XO); s.wait_n = rp.styl_parts; s.out_group = G(0, G_XIN); s.out_slot = 0;
-        s.in0 = XO(NL - 1); s.out = xin0;
-        st.push_back(s);
-    }
-    for (Stage& s : st) {
-        if (s.blkstride == 0) s.blkstride = 1;                        // every other stage visits every block
-        if (s.out_rep == 0) s.out_rep = 1;                            // one flag, one line
-        s.xcd = -1;
-    }
-    if ((int)st.size() != L.nwg || st.size() > 256) return LADIFF_ERR_SHAPE;
-    if (g_xcd_local && xcd_round_robin()) sys_place_stages(st);
-    host.resize(st.size() * sizeof(Stage));
-    std::memcpy(host.data(), st.data(), host.size());
-    return 0;
+    return sys_build_stages(W, WS, ws, MR, NB, g_xcd_local && xcd_round_robin(), host);
 }
 
 // One launch = local steps [step_lo, step_lo + n) of the loop on the latents in `lat`.  The stage table must already be in
@@ -2655,6 +2311,20 @@ std::atomic<int> g_waves16{2};
 // hand-off protocol of the 16-row plan's eight-wave stages: 1 = parity tags in the data (default), 0 = flags (ladiff_debug_set_handoff)
 std::atomic<int> g_handoff{1};
 constexpr int LOOK_AHEAD_BLOCKS = 72;      // see `settle`: 58 blocks (128 prompts of mixed lengths) lose with it, 86 win
+
+namespace {
+// Every instantiation of the kernel, once: the launch opts each into its dynamic LDS and selects by the same rows.
+struct LoopKernel { int fp32, MR, waves, tagged; bool look_ahead; void (*fn)(const SysArgs); int threads; };
+#define LOOP_KERNEL(AR, MR, WS, HO, EQ) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ>, 256 * WS}
+const LoopKernel LOOP_KERNELS[] = {
+    // flags: 16-row blocks with two waves per SIMD (ladiff_debug_set_handoff(0)) and 32-row blocks, split | fp32
+    LOOP_KERNEL(0, 1, 2, 0, false), LOOP_KERNEL(0, 2, 1, 0, false), LOOP_KERNEL(1, 1, 2, 0, false), LOOP_KERNEL(1, 2, 1, 0, false),
+    LOOP_KERNEL(0, 1, 1, 0, false), LOOP_KERNEL(1, 1, 1, 0, false),        // 16-row blocks, one wave per SIMD (ladiff_debug_set_stage_waves(1))
+    LOOP_KERNEL(0, 1, 2, 1, false), LOOP_KERNEL(1, 1, 2, 1, false),        // tags: the 16-row plan that ships
+    LOOP_KERNEL(0, 1, 2, 1, true), LOOP_KERNEL(1, 1, 2, 1, true),          // tags with look-ahead (SysArgs::look_ahead)
+};
+#undef LOOP_KERNEL
+}  // namespace
 
 int sys_reset_status(float* ws, hipStream_t s) {
     const SysLayout L = sys_layout(2, 1);            // the status words sit at a fixed offset (before everything sized by the plan)
@@ -2710,12 +2380,8 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     if (dev < 0 || dev >= 64) return LADIFF_ERR_ARG;
     std::lock_guard<std::mutex> lock(mu);
     if (!attr_set[dev]) {
-        const void* k[10] = {reinterpret_cast<const void*>(systolic_loop_kernel<1, 0, 2, 0>), reinterpret_cast<const void*>(systolic_loop_kernel<2, 0, 1, 0>),
-                             reinterpret_cast<const void*>(systolic_loop_kernel<1, 1, 2, 0>), reinterpret_cast<const void*>(systolic_loop_kernel<2, 1, 1, 0>),
-                             reinterpret_cast<const void*>(systolic_loop_kernel<1, 0, 1, 0>), reinterpret_cast<const void*>(systolic_loop_kernel<1, 1, 1, 0>),
-                             reinterpret_cast<const void*>(systolic_loop_kernel<1, 0, 2, 1>), reinterpret_cast<const void*>(systolic_loop_kernel<1, 1, 2, 1>),
-                             reinterpret_cast<const void*>(systolic_loop_kernel<1, 0, 2, 1, true>), reinterpret_cast<const void*>(systolic_loop_kernel<1, 1, 2, 1, true>)};
-        for (int i = 0; i < 10; ++i) LADIFF_HIP(hipFuncSetAttribute(k[i], hipFuncAttributeMaxDynamicSharedMemorySize, SYS_LDS_BYTES));
+        for (const LoopKernel& k : LOOP_KERNELS)
+            LADIFF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, SYS_LDS_BYTES));
         attr_set[dev] = true;
     }
     if (done[dev] == nullptr) LADIFF_HIP(hipEventCreateWithFlags(&done[dev], hipEventDisableTiming));
@@ -2731,25 +2397,17 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     } else {
         LADIFF_HIP(hipMemsetAsync(a.flags, 0, (L.off_xin0 - L.off_flags) * sizeof(float), s));
     }
-    if (fp32) {
-        if (tagged && a.look_ahead) hipLaunchKernelGGL((systolic_loop_kernel<1, 1, 2, 1, true>), dim3(L.nwg), dim3(512), SYS_LDS_BYTES, s, a);
-        else if (tagged) hipLaunchKernelGGL((systolic_loop_kernel<1, 1, 2, 1>), dim3(L.nwg), dim3(512), SYS_LDS_BYTES, s, a);
-        else if (MR == 1 && g_waves16 == 2) hipLaunchKernelGGL((systolic_loop_kernel<1, 1, 2, 0>), dim3(L.nwg), dim3(512), SYS_LDS_BYTES, s, a);
-        else if (MR == 1) hipLaunchKernelGGL((systolic_loop_kernel<1, 1, 1, 0>), dim3(L.nwg), dim3(256), SYS_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((systolic_loop_kernel<2, 1, 1, 0>), dim3(L.nwg), dim3(256), SYS_LDS_BYTES, s, a);
-    } else {
-        if (tagged && a.look_ahead) hipLaunchKernelGGL((systolic_loop_kernel<1, 0, 2, 1, true>), dim3(L.nwg), dim3(512), SYS_LDS_BYTES, s, a);
-        else if (tagged) hipLaunchKernelGGL((systolic_loop_kernel<1, 0, 2, 1>), dim3(L.nwg), dim3(512), SYS_LDS_BYTES, s, a);
-        else if (MR == 1 && g_waves16 == 2) hipLaunchKernelGGL((systolic_loop_kernel<1, 0, 2, 0>), dim3(L.nwg), dim3(512), SYS_LDS_BYTES, s, a);
-        else if (MR == 1) hipLaunchKernelGGL((systolic_loop_kernel<1, 0, 1, 0>), dim3(L.nwg), dim3(256), SYS_LDS_BYTES, s, a);
-        else hipLaunchKernelGGL((systolic_loop_kernel<2, 0, 1, 0>), dim3(L.nwg), dim3(256), SYS_LDS_BYTES, s, a);
-    }
+    // the key of LOOP_KERNELS: 32-row blocks have one form; look-ahead is a property of the tagged hand-off
+    const int mr = MR == 1 ? 1 : 2, waves = mr == 1 && g_waves16 == 2 ? 2 : 1;
+    const bool la = tagged && a.look_ahead;
+    const LoopKernel* k = nullptr;
+    for (const LoopKernel& c : LOOP_KERNELS)
+        if (c.fp32 == (fp32 ? 1 : 0) && c.MR == mr && c.waves == waves && c.tagged == (tagged ? 1 : 0) && c.look_ahead == la) k = &c;
+    if (k == nullptr) return LADIFF_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k->fn, dim3(L.nwg), dim3(k->threads), SYS_LDS_BYTES, s, a);
     LADIFF_LAUNCH_CHECK();
     LADIFF_HIP(hipEventRecord(done[dev], s));
     return 0;
 }
-
-size_t sys_blocks_offset_floats(int MR, int NB) { return sys_layout(MR, NB).off_blocks; }
-size_t sys_status_offset_floats(int B, int T) { (void)B; (void)T; return sys_layout(2, 1).off_status; }
 
 }  // namespace ladiff

@@ -5,7 +5,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "../../include/ladiff_hip.h"   // the model's dimensions; nothing of HIP: host-only units include this header too (systolic_plan.h)
 
 namespace ladiff {
 
@@ -79,7 +79,7 @@ struct ClipW {                                                       // text sid
     const float* pos;                                                // position_embedding [77, 768]
     NormW final_ln;
     const float* proj;                                               // text_projection.weight [768, 768], no bias
-    ClipLayerW layer[CLIP_MAX_LAYERS];                               // a shallower model fills a prefix (rest NULL)
+    ClipLayerW layer[LADIFF_CLIP_MAX_LAYERS];                        // a shallower model fills a prefix (rest NULL)
 };
 
 constexpr int DEN_NPARAMS = sizeof(DenoiserW) / sizeof(const float*);
