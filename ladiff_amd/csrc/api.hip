@@ -26,57 +26,6 @@ bool load_weights(W& dst, const float* const* ptrs) {
     return true;
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// ---- reverse-loop workspace carve-up (floats)
-struct ReverseWs {
-    float *tables, *cache, *latents, *eps, *fwd, *sys, *cws;
-    int32_t* d_step;
-    size_t fwd_floats, cws_floats, total_bytes, sys_off;      // sys_off: floats from the workspace base to `sys`
-    int window;                            // steps whose c-table rows are resident at a time
-};
-// The hoisted cross-attention table is [9][steps][2B+1][256] floats: 118 MB for 50 steps at B = 128, but 2.4 GB for a
-// 1000-step DDPM schedule.  Long schedules are run window by window (the largest divisor of n_steps that is <= 64 and a
-// multiple of 10, so that the step graphs unroll ten-fold; failing that the largest divisor <= 64 of any kind), the table rebuilt
-// before each window from the per-layer LN(value) rows kept in the cache.  A window never exceeds REVERSE_WINDOW_MAX steps, and the
-// carve reserves the table for min(n_steps, REVERSE_WINDOW_MAX) steps whatever the window: the workspace query is then non-decreasing
-// in n_steps (a 65-step schedule used to keep a 65-step table and ask for more than a 1000-step one).  A schedule longer than 64 steps
-// with few divisors pays in table rebuilds (a prime length rebuilds per step), not in memory.
-constexpr int REVERSE_WINDOW_MAX = 64;
-int reverse_window(int n) {
-    if (n <= REVERSE_WINDOW_MAX) return n;
-    for (int w = REVERSE_WINDOW_MAX; w >= 10; --w)
-        if (n % w == 0 && w % 10 == 0) return w;
-    for (int w = REVERSE_WINDOW_MAX; w > 1; --w)
-        if (n % w == 0) return w;
-    return 1;
-}
-ReverseWs carve_reverse(void* ws, int B, int T, int n, int ntxt = 1) {
-    ReverseWs r;
-    const int B2 = 2 * B;
-    size_t off = 0;
-    auto take = [&](size_t floats) { float* p = ws ? reinterpret_cast<float*>(ws) + off : nullptr; off += align_up(floats, 64); return p; };
-    r.d_step = reinterpret_cast<int32_t*>(take(64));
-    r.tables = take(den_tables_floats(n));
-    r.window = reverse_window(n);
-    const int wcap = n < REVERSE_WINDOW_MAX ? n : REVERSE_WINDOW_MAX;  // >= r.window; sized by it so that the query never shrinks with n
-    r.cache = take(den_text_cache_floats(B2, wcap, ntxt));             // the c table is the cache's last part: r.window steps of it are used
-    r.latents = take((size_t)B * T * D);
-    r.eps = take((size_t)B2 * T * D);
-    size_t pre = (size_t)n * D * 3;                                    // time-table scratch
-    const size_t txt = den_text_ws_floats(B2, 1, ntxt);                // text-cache scratch (static part)
-    if (txt > pre) pre = txt;
-    r.fwd_floats = den_forward_ws_floats(B2, T);
-    if (pre > r.fwd_floats) r.fwd_floats = pre;
-    r.fwd = take(r.fwd_floats);
-    r.sys_off = off;
-    r.sys = take(sys_ws_floats(B, T));                                 // block buffers, flags and stage table of the pipeline loop
-    r.cws_floats = (size_t)NL * wcap * (B2 + 1) * D;                   // scratch of the c-table builder (all layers' input rows)
-    r.cws = take(r.cws_floats);
-    r.total_bytes = off * sizeof(float);
-    return r;
-}
-
 struct Sampler {
     hipGraphExec_t exec = nullptr;
     hipGraphExec_t setup = nullptr;       // per-call prologue (text cache, initial latents, counter reset, first network input)
@@ -282,14 +231,10 @@ int ladiff_decoder_cross_attention(const float* q, const float* kv, const int32_
 size_t ladiff_denoiser_tables_floats(int n_steps) { return den_tables_floats(n_steps); }
 size_t ladiff_denoiser_text_cache_floats(int B2, int n_steps, int n_text) { return den_text_cache_floats(B2, n_steps, n_text); }
 size_t ladiff_denoiser_workspace_bytes(int B2, int T, int n_steps, int n_text) {
-    size_t f = den_forward_ws_floats(B2, T);
-    const size_t a = (size_t)n_steps * D * 3, b = den_text_ws_floats(B2, n_steps, n_text);
-    if (a > f) f = a;
-    if (b > f) f = b;
-    // n_text > 1 switches the text cache to another algorithm with less scratch: never less than the one-token form asks for, so that the
-    // query is non-decreasing in every argument
-    if (n_text > 1) { const size_t c = den_text_ws_floats(B2, n_steps, 1); if (c > f) f = c; }
-    return f * sizeof(float);
+    // the largest of the three entries' layouts.  n_text > 1 switches the text cache to another algorithm with less scratch: never less
+    // than the one-token form asks for, so that the query is non-decreasing in every argument
+    return sizeof(float) * std::max({den_forward_ws_floats(B2, T), den_time_layout(nullptr, n_steps).total,
+                                     den_text_ws_floats(B2, n_steps, n_text), den_text_ws_floats(B2, n_steps, 1)});
 }
 // The three denoiser entries share one query, but none of them takes all of its arguments: each refuses a workspace below the query at
 // its OWN arguments (the ones it does not take at 1).  The query is non-decreasing, so this is never more than the caller's query.

@@ -15,8 +15,8 @@
 
 namespace ladiff {
 
-constexpr int CW = LADIFF_TEXT_DIM;        // 768
-constexpr int CFF = 4 * CW;                // 3072
+constexpr int CW = CLIP_W;                 // 768 (workspace.h)
+constexpr int CFF = CLIP_FF;               // 3072
 constexpr int CH = CW / 64;                // 12 heads
 constexpr int CNV = CW / 256;              // f32x4 per lane in a one-wave row
 
@@ -120,32 +120,7 @@ static int ln_rows(const float* x, const int32_t* eos, int L, const NormW& n, in
     return 0;
 }
 
-// Few rows (a demo.py call: the empty prompt + one prompt = ~40 rows; round 6): the 128-row tiles of the large-M GEMM leave N / 128 =
-// 6 .. 24 workgroups, each walking the whole K - 45 us per GEMM whatever its size, 1.9 of a single prompt's 10 ms (profiles/r6/11_*).
-// Up to CLIP_SMALL_ROWS rows the split mode's GEMMs run on the denoiser's K-resident 64x64 tiles instead (gemm_kr.hip: one 256-wide
-// K slice per workgroup, K / 256 = 3 or 12 partial planes, 36 .. 144 workgroups that each move 64 KB) and a row pass sums the
-// planes and applies bias / quick_gelu / residual: the same S-format operands and split products, summed per K slice.
-constexpr int CLIP_SMALL_ROWS = 256;
-constexpr int CLIP_PLANE_COLS = 12 * CW;       // floats per row of the partial planes: max over the GEMMs of (K / 256) * N = 3 * 3072 = 12 * 768 = 9216
-
-// Many rows: fc2 (K = 3072, N = 768) is 6 column tiles x a few dozen row tiles - about one workgroup per CU, each walking 96 K stages with
-// ONE stage in flight (70 us at 2,260 rows, most of it load latency nobody hides).  Its K range is cut in CLIP_FC2_KPARTS parts over
-// blockIdx.y (GemmArgs::ksplit: four times the workgroups, two per CU hiding each other's stages) and the row pass sums the planes.
-constexpr int CLIP_FC2_KPARTS = 4;
-constexpr int CLIP_FC2_KPARTS_MAX_ROWS = 8192;  // beyond, the tiles alone fill the chip
-// Plane space for M rows: the largest need of any regime a call with AT MOST M rows can land in (small-row planes up to CLIP_SMALL_ROWS
-// rows, fc2's K parts up to CLIP_FC2_KPARTS_MAX_ROWS, none beyond), so that the workspace query never shrinks when the row count grows: a
-// caller that sizes its workspace once for its largest batch is served at every smaller one.  The carve below takes the same amount.
-static size_t clip_plane_floats(int M) {
-    const size_t small_rows = (size_t)(M < CLIP_SMALL_ROWS ? M : CLIP_SMALL_ROWS) * CLIP_PLANE_COLS;
-    const size_t kparts = M > CLIP_SMALL_ROWS ? (size_t)(M < CLIP_FC2_KPARTS_MAX_ROWS ? M : CLIP_FC2_KPARTS_MAX_ROWS) * CLIP_FC2_KPARTS * CW : 0;
-    return small_rows > kparts ? small_rows : kparts;
-}
-size_t clip_ws_floats_rows(int B, int M) {
-    return (size_t)M * (2 * CW /*x ping-pong*/ + CW /*h*/ + 3 * CW /*qkv*/ + CW /*att*/ + CFF /*mlp*/) + (size_t)B * CW + (size_t)B + 64 +
-           clip_plane_floats(M);
-}
-size_t clip_ws_floats(int B, int L) { return clip_ws_floats_rows(B, B * L); }
+// The row-count regimes (CLIP_SMALL_ROWS, CLIP_FC2_KPARTS, CLIP_FC2_KPARTS_MAX_ROWS) and the plane space they need: workspace.h
 
 // y = act(sum_k planes[k] + bias) + res over [M, N] (N % 4 == 0): fp32 and / or S-format; planes [np][M][ld]
 __global__ __launch_bounds__(256) void clip_reduce_kernel(const float* __restrict__ planes, int np, size_t plane, int ld, int M, int N,
@@ -179,21 +154,14 @@ int clip_text_encode(const ClipW& w, const ClipW* wsp, int n_layers, int vocab, 
         return LADIFF_ERR_SHAPE;
     const bool ragged = row_off != nullptr;
     if (ragged && (seq_len == nullptr || row_seq == nullptr || total_rows < B || (long long)total_rows > (long long)B * L)) return LADIFF_ERR_ARG;
-    if (ws_floats < (ragged ? clip_ws_floats_rows(B, total_rows) : clip_ws_floats(B, L))) return LADIFF_ERR_WORKSPACE;
-    if (B == 0) return 0;
     const int M = ragged ? total_rows : B * L;
+    const ClipWs a = clip_layout(ws, B, M);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
+    if (B == 0) return 0;
     const bool sp = wsp != nullptr;
-    float* p = ws;
-    float* x = p; p += (size_t)M * CW;          // residual stream, ping-pong with x2 across the two sub-blocks
-    float* x2 = p; p += (size_t)M * CW;
-    float* h = p; p += (size_t)M * CW;          // LN output (S-format in split mode)
-    float* qkv = p; p += (size_t)M * 3 * CW;
-    float* att = p; p += (size_t)M * CW;
-    float* mlp = p; p += (size_t)M * CFF;
+    float *x = a.x, *x2 = a.x2, *h = a.h, *qkv = a.qkv, *att = a.att, *mlp = a.mlp, *planes = a.planes, *pooled = a.pooled;
+    int32_t* eos = a.eos;
     const bool small = sp && M <= CLIP_SMALL_ROWS;
-    float* planes = p; p += clip_plane_floats(M);   // partial planes: [K / 256][M][ld] of the small-row path, [CLIP_FC2_KPARTS][M][768] of fc2 otherwise (16-byte aligned: every size so far is a multiple of 768 floats)
-    float* pooled = p; p += (size_t)B * CW;
-    int32_t* eos = reinterpret_cast<int32_t*>(p);
 
     // small-row path: S-format A [M, K] x S-format W [N, K] -> K / 256 planes (row stride ld, written at column col0) ...
     auto kr_planes = [&](const float* A, int K, const float* Wsp, int N, int ld, int col0) -> int {

@@ -3,13 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/ladiff_hip.h"
+#include "weights.h"      // the model's dimensions (D, H, DH, ...): shared with the host-only units
 
 namespace ladiff {
 
-constexpr int D = 256;     // latent / model width      (config_ladiff_humanml3d.yaml:132 latent_dim[-1])
-constexpr int H = 4;       // heads                     (configs/modules/denoiser.yaml:7)
-constexpr int DH = 64;     // head dim
 constexpr float LN_EPS = 1e-5f;
 constexpr int CLIP_MAX_LAYERS = LADIFF_CLIP_MAX_LAYERS;
 constexpr int CLIP_MAX_POSITIONS = LADIFF_CLIP_MAX_POSITIONS;

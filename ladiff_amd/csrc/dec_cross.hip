@@ -558,8 +558,6 @@ __global__ __launch_bounds__(512, 1) void dec_out_cross_kernel(const OutCrossArg
     }
 }
 
-size_t dec_cross_ws_floats(int B, int T) { return (size_t)B * H * T * (2 * D + 1); }
-
 // per-device kernel attribute (T = 8 needs 64.1 KiB of dynamic LDS): once per device, under a mutex, outside any stream capture
 // (the graphed decode calls it before it begins to capture)
 int dec_cross_prepare() {

@@ -30,12 +30,6 @@ static GemmArgs lin(const float* A, int lda, const float* W, const float* bias, 
     return g;
 }
 
-// rows = B * F for the padded layout, or the sum of the lengths for the ragged one
-size_t dec_ws_floats(int B, size_t rows, int T) {
-    return rows * (16 * D + 3 * D + D + FF) + (rows + 63) / 64 * 64 + (size_t)NL * ((size_t)T * B * 2 * D + dec_cross_ws_floats(B, T)) +
-           (size_t)LADIFF_MAX_FRAMES * (2 * D + 3 * D);       // layer 0: the position table as a GEMM operand and its q|k|v
-}
-
 // wsp != nullptr selects the f16x3 matrix path (S-format copies of the weight matrices in `wsp`, GEMM operands in
 // S-format, LayerNorm as a row kernel after each fused GEMM); see denoiser.hip and common.h.
 // row_off != nullptr (B + 1 entries, row_off[B] = R): RAGGED rows - sample b owns rows [row_off[b], row_off[b] + lengths[b]) and
@@ -48,7 +42,8 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
     const bool ragged = row_off != nullptr;
     if (ragged && (R < 0 || (size_t)R > (size_t)B * F)) return LADIFF_ERR_SHAPE;
     const int M = ragged ? R : B * F;
-    if (ws_floats < dec_ws_floats(B, (size_t)M, T)) return LADIFF_ERR_WORKSPACE;
+    DecWs a = dec_layout(ws, B, (size_t)M, T);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     if (M == 0) return 0;
 #ifdef LADIFF_STAMPS
     const char* dec_cut_env = getenv("LADIFF_DEC_CUT");
@@ -57,23 +52,11 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
     if (dec_cut == 0) return 0;
 #endif
     const bool sp = wsp != nullptr;
-    const size_t MD = (size_t)M * D;
-    float* P[4]; float* SK[NSKIP]; float* Ps[4]; float* SKs[NSKIP];
-    float* p = ws;
-    for (int i = 0; i < 4; ++i) { P[i] = p; p += MD; }
-    for (int i = 0; i < NSKIP; ++i) { SK[i] = p; p += MD; }
-    for (int i = 0; i < 4; ++i) { Ps[i] = sp ? p : nullptr; p += MD; }
-    for (int i = 0; i < NSKIP; ++i) { SKs[i] = sp ? p : nullptr; p += MD; }
-    float* qkv = p; p += 3 * MD;
-    float* att = p; p += MD;
-    float* hid = p; p += (size_t)M * FF;
-    float* kv = p; p += (size_t)NL * T * B * 2 * D;      // memory K | V of every layer
-    float* guws = p; p += (size_t)NL * dec_cross_ws_floats(B, T);   // G | U | c of the folded cross-attention of every layer (dec_cross.hip)
-    int32_t* row_out = reinterpret_cast<int32_t*>(p); p += ((size_t)M + 63) / 64 * 64;   // ragged: place of each row in the padded output (rounded: what follows is read 16 bytes at a time and by LDS-DMA)
-    float* pex = p; p += (size_t)LADIFF_MAX_FRAMES * D;   // layer 0: pe[:F] (+ S-format twin) and its in_proj, shared by all samples
-    float* pexs = p; p += (size_t)LADIFF_MAX_FRAMES * D;
-    float* qkv0 = p;
-    const size_t kv_l = (size_t)T * B * 2 * D, gu_l = dec_cross_ws_floats(B, T);
+    if (!sp) { for (float*& t : a.Ps) t = nullptr; for (float*& t : a.SKs) t = nullptr; }      // fp32 mode: no S-format twins
+    float *const *P = a.P, *const *SK = a.SK, *const *Ps = a.Ps, *const *SKs = a.SKs;
+    float *qkv = a.qkv, *att = a.att, *hid = a.hid, *kv = a.kv, *guws = a.guws, *pex = a.pex, *pexs = a.pexs, *qkv0 = a.qkv0;
+    int32_t* row_out = a.row_out;
+    const size_t kv_l = a.kv_layer, gu_l = a.gu_layer;
 
     // The memory side of every layer's cross-attention depends on z and the weights only: the nine K | V projections and the
     // nine folds into G | U | c run up front, one launch each (fp32 in both modes).   cross_attention.py:373-376
@@ -226,7 +209,7 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         // rows.  The tiles need Np = ceil(C / 128) 128 weight rows: the library pads the caller's C rows ITSELF (a 1-KiB-per-row copy
         // into the in_proj buffer, free by now) - a table of exactly C rows is never read past its end.
         const int Np = (C + 127) / 128 * 128;
-        if ((size_t)Np > (size_t)FF || (size_t)Np * (D + 1) > 3 * MD) return LADIFF_ERR_SHAPE;
+        if ((size_t)M * Np > a.hid_floats || (size_t)Np * (D + 1) > a.qkv_floats) return LADIFF_ERR_SHAPE;      // the two buffers it re-uses
         float* wpad = qkv; float* bpad = qkv + (size_t)Np * D;
         LADIFF_TRY(launch_pad_rows(wsp->final_layer.w, w.final_layer.b, wpad, bpad, C, Np, s)); DEC_CUT();
         GemmArgs g = lin(curs, D, wpad, bpad, hid, Np, M, Np, D);

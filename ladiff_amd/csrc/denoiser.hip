@@ -81,15 +81,12 @@ static GemmArgs lin(const float* A, int lda, const LinearW& l, float* Y, int ldy
 }
 
 // ------------------------------------------------------------------ time tables
-size_t den_tables_floats(int n_steps) { return (size_t)n_steps * DEN_STEP_STRIDE; }
-static size_t time_ws_floats(int n) { return (size_t)n * D * 3; }
-
 int denoiser_time_tables(const DenoiserW& w, const float* sinus, int n, float* tables, float* ws, size_t ws_floats,
                          hipStream_t s) {
-    if (ws_floats < time_ws_floats(n)) return LADIFF_ERR_WORKSPACE;
-    float* h1 = ws;                 // SiLU(linear_1(sinusoid))       tools/embeddings.py:296-301
-    float* temb = h1 + (size_t)n * D;   // time_emb                     :303
-    float* semb = temb + (size_t)n * D; // SiLU(time_emb), input of every StylizationBlock.emb_layers
+    const DenTimeWs t = den_time_layout(ws, n);
+    if (ws_floats < t.total) return LADIFF_ERR_WORKSPACE;
+    // h1 = SiLU(linear_1(sinusoid)), temb = time_emb, semb = SiLU(time_emb), input of every StylizationBlock.emb_layers   tools/embeddings.py:296-303
+    float *h1 = t.h1, *temb = t.temb, *semb = t.semb;
     LADIFF_TRY(launch_gemm(lin(sinus, TEXT_DIM, w.time1, h1, D, n, D, TEXT_DIM, ACT_SILU), s));
     LADIFF_TRY(launch_gemm(lin(h1, D, w.time2, temb, D, n, D, D), s));
     LADIFF_TRY(launch_silu(temb, semb, (size_t)n * D, s));
@@ -105,39 +102,25 @@ int denoiser_time_tables(const DenoiserW& w, const float* sinus, int n, float* t
     return 0;
 }
 
-// ------------------------------------------------------------------ text cache
-//   [B2,256]              emb_proj(text)                      (ladiff_denoiser.py:198)
-//   [9][B2,512]           K | V of the text token per layer   (sa_block in_proj rows 256..767)
-//   [9][n][B2+1,256]      c table: the whole ca_block delta   (mdiff_transformer.py:219-247 with ONE text token)
+// ------------------------------------------------------------------ text cache (den_text_cache_layout, workspace.h)
+//   tproj  emb_proj(text)                      (ladiff_denoiser.py:198)
+//   tkv    K | V of the text token per layer   (sa_block in_proj rows 256..767)
+//   ctab   c table: the whole ca_block delta   (mdiff_transformer.py:219-247 with ONE text token)
 // With one text token softmax(key) over the token axis is exactly 1 and sum_d softmax(query)_d = 1, so the attention
 // output of a valid latent row is the value vector v_b of its sample and of a padded row is 0; the block then adds
 //   c[step, layer, b]   = out( SiLU( LN(v_b) * (1 + scale) + shift ) )     for valid rows
 //   c[step, layer, pad] = out( SiLU( beta    * (1 + scale) + shift ) )     for padded rows (LN(0) = beta)
 // which depends on (step, layer, sample) only - never on the latents - so it is computed once per call for every
 // step instead of 9 x n_steps times inside the loop.
-// ntxt > 1 (general-N conditioning, linear_ca.hip): [B2 N,256] projected tokens, [9][B2 N,512] K|V of the text tokens,
-// [9][B2][4][64][64] the cross-attention's key^T value matrices (text only, so step-invariant) instead of the c table
-size_t den_text_cache_floats(int B2, int n, int ntxt) {
-    if (ntxt > 1) return (size_t)B2 * ntxt * D + (size_t)NL * B2 * ntxt * 2 * D + (size_t)NL * B2 * H * DH * DH;
-    return (size_t)B2 * D + (size_t)NL * B2 * 2 * D + (size_t)NL * B2 * D + (size_t)NL * n * (B2 + 1) * D;
-}
-size_t den_text_ws_floats(int B2, int n, int ntxt) {
-    if (ntxt > 1) return (size_t)B2 * ntxt * (TEXT_DIM + 3 * D);
-    // relu(text) | per-layer LN(text projection) | c-table inputs of all layers (the per-layer launches are batched)
-    return (size_t)B2 * TEXT_DIM + (size_t)NL * B2 * D + (size_t)NL * n * (B2 + 1) * D;
-}
-
+// ntxt > 1 (general-N conditioning, linear_ca.hip): the projected tokens, the K|V of the text tokens and the cross-attention's
+// key^T value matrices (text only, so step-invariant) instead of the c table
 static int denoiser_text_cache_general(const DenoiserW& w, const float* text, int B2, int N, float* cache, float* ws, size_t ws_floats,
                                        hipStream_t s) {
     const int R = B2 * N;
-    if (ws_floats < den_text_ws_floats(B2, 1, N)) return LADIFF_ERR_WORKSPACE;
-    float* rl = ws;
-    float* tn = rl + (size_t)R * TEXT_DIM;
-    float* key = tn + (size_t)R * D;
-    float* val = key + (size_t)R * D;
-    float* tproj = cache;
-    float* tkv = cache + (size_t)R * D;
-    float* catt = tkv + (size_t)NL * R * 2 * D;
+    const DenTextWs t = den_text_layout(ws, B2, 1, N);
+    if (ws_floats < t.total) return LADIFF_ERR_WORKSPACE;
+    const DenTextCache c = den_text_cache_layout(cache, B2, 1, N);
+    float *rl = t.rl, *tn = t.tn, *key = t.key, *val = t.val, *tproj = c.tproj, *tkv = c.tkv, *catt = c.catt;
     LADIFF_TRY(launch_relu(text, rl, (size_t)R * TEXT_DIM, s));
     LADIFF_TRY(launch_gemm(lin(rl, TEXT_DIM, w.emb_proj, tproj, D, R, D, TEXT_DIM), s));          // ladiff_denoiser.py:198
     for (int l = 0; l < NL; ++l) {
@@ -152,21 +135,12 @@ static int denoiser_text_cache_general(const DenoiserW& w, const float* text, in
     return 0;
 }
 
-// cache layout, one text token: [B2,256] emb_proj | [9][B2,512] text K|V | [9][B2,256] LN(value) rows | [9][n][B2+1,256] c table
-const float* den_cache_tkv(const float* cache, int B2, int ntxt) { return cache + (size_t)B2 * ntxt * D; }
-const float* den_cache_ctab(const float* cache, int B2, int ntxt) {
-    const float* p = den_cache_tkv(cache, B2, ntxt) + (size_t)NL * B2 * ntxt * 2 * D;
-    return ntxt > 1 ? p : p + (size_t)NL * B2 * D;
-}
-
 // the part of the text cache that does not depend on the step: once per call
 int denoiser_text_static(const DenoiserW& w, const float* text, int B2, float* cache, float* ws, size_t ws_floats, hipStream_t s) {
-    if (ws_floats < (size_t)B2 * (TEXT_DIM + NL * D)) return LADIFF_ERR_WORKSPACE;
-    float* rl = ws;
-    float* tn = rl + (size_t)B2 * TEXT_DIM;                  // [NL][B2][256]
-    float* tproj = cache;
-    float* tkv = cache + (size_t)B2 * D;
-    float* nval = tkv + (size_t)NL * B2 * 2 * D;
+    const DenTextWs t = den_text_layout(ws, B2, 0, 1);      // no step: the c-table inputs are denoiser_ctab's
+    if (ws_floats < t.total) return LADIFF_ERR_WORKSPACE;
+    const DenTextCache c = den_text_cache_layout(cache, B2, 0, 1);
+    float *rl = t.rl, *tn = t.tn, *tproj = c.tproj, *tkv = c.tkv, *nval = c.nval;
     LADIFF_TRY(launch_relu(text, rl, (size_t)B2 * TEXT_DIM, s));
     LADIFF_TRY(launch_gemm(lin(rl, TEXT_DIM, w.emb_proj, tproj, D, B2, D, TEXT_DIM), s));
     // the nine layers' projections of the text token are independent and tiny: one launch per kind, not per layer
@@ -192,10 +166,12 @@ int denoiser_text_static(const DenoiserW& w, const float* text, int B2, float* c
 int denoiser_ctab(const DenoiserW& w, const float* tables_lo, int n, float* cache, int B2, float* u, size_t u_floats, hipStream_t s,
                   const DenoiserW* wsp) {
     const int R = B2 + 1;
-    if (u_floats < (size_t)n * R * D) return LADIFF_ERR_WORKSPACE;
-    const float* nval = cache + (size_t)B2 * D + (size_t)NL * B2 * 2 * D;
-    float* ctab = const_cast<float*>(den_cache_ctab(cache, B2, 1));
-    if (u_floats >= (size_t)NL * n * R * D) {                // all layers at once: one input launch, one batched GEMM
+    const size_t u_all = den_text_layout(nullptr, B2, n, 1).u_floats;      // the input rows of all layers
+    if (u_floats < u_all / NL) return LADIFF_ERR_WORKSPACE;
+    const DenTextCache c = den_text_cache_layout(cache, B2, n, 1);
+    const float* nval = c.nval;
+    float* ctab = c.ctab;
+    if (u_floats >= u_all) {                                 // all layers at once: one input launch, one batched GEMM
         RowBatch rb;
         GemmArgs g[NL];
         for (int l = 0; l < NL; ++l) {
@@ -221,27 +197,22 @@ int denoiser_ctab(const DenoiserW& w, const float* tables_lo, int n, float* cach
 int denoiser_text_cache(const DenoiserW& w, const float* text, int B2, const float* tables, int n, float* cache,
                         float* ws, size_t ws_floats, hipStream_t s, int ntxt) {
     if (ntxt > 1) return denoiser_text_cache_general(w, text, B2, ntxt, cache, ws, ws_floats, s);
-    if (ws_floats < den_text_ws_floats(B2, n)) return LADIFF_ERR_WORKSPACE;
+    const DenTextWs t = den_text_layout(ws, B2, n, 1);
+    if (ws_floats < t.total) return LADIFF_ERR_WORKSPACE;
     LADIFF_TRY(denoiser_text_static(w, text, B2, cache, ws, ws_floats, s));
-    float* u = ws + (size_t)B2 * (TEXT_DIM + NL * D);
-    return denoiser_ctab(w, tables, n, cache, B2, u, ws_floats - (size_t)B2 * (TEXT_DIM + NL * D), s, nullptr);
+    return denoiser_ctab(w, tables, n, cache, B2, t.u, t.u_floats, s, nullptr);
 }
 
 // ------------------------------------------------------------------ one ca_block, literal (unit entry for the N > 1 path)
 // out = x + StylizationBlock( softmax_d(query(LN x)) . sum_n softmax_n(key(LN_t xf)) value(LN_t xf)^T , emb )   :219-247
-size_t linear_cross_attention_ws_floats(int B, int T, int N) {
-    return (size_t)B * N * 3 * D + (size_t)B * H * DH * DH + (size_t)B * T * 2 * D + (size_t)B * 3 * D;
-}
 int linear_cross_attention(const DenoiserW& w, int layer, const float* x, const float* xf, const float* emb, const int32_t* counts,
                            int B, int T, int N, float* out, float* ws, size_t ws_floats, hipStream_t s) {
     if (layer < 0 || layer >= NL || T < 1 || T > LADIFF_MAX_LATENTS || N < 1) return LADIFF_ERR_SHAPE;
-    if (ws_floats < linear_cross_attention_ws_floats(B, T, N)) return LADIFF_ERR_WORKSPACE;
+    const LcaWs a = lca_layout(ws, B, T, N);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     const DenLayerW& L = w.layer[layer];
     const int R = B * N, M = B * T;
-    float* tn = ws; float* key = tn + (size_t)R * D; float* val = key + (size_t)R * D;
-    float* catt = val + (size_t)R * D;
-    float* xn = catt + (size_t)B * H * DH * DH; float* q = xn + (size_t)M * D;
-    float* semb = q + (size_t)M * D; float* mod = semb + (size_t)B * D;
+    float *tn = a.tn, *key = a.key, *val = a.val, *catt = a.catt, *xn = a.xn, *q = a.q, *semb = a.semb, *mod = a.mod;
     LADIFF_TRY(launch_layernorm(xf, L.ca_text_norm.g, L.ca_text_norm.b, tn, R, s));
     LADIFF_TRY(launch_gemm(lin(tn, D, L.ca_key, key, D, R, D, D), s));
     LADIFF_TRY(launch_gemm(lin(tn, D, L.ca_value, val, D, R, D, D), s));
@@ -273,13 +244,6 @@ int linear_cross_attention(const DenoiserW& w, int layer, const float* x, const 
 // f16x3 mode (8 launches, 9 on the output blocks): the same arithmetic with the steps grouped into fused kernels -
 //   [skip] gemm_rowln (concat GEMM + bias) | qkv_attn (qkv + att) | gemm_rowln (R1, X1) | linear1 | linear2 split-K |
 //   reduce_rows (X3) | ffn.linear1 | ffn.linear2 split-K | combine_gemm (u, x').
-size_t den_forward_ws_floats(int B2, int T) { return (size_t)B2 * T * (16 * D + 3 * D + D + FF + 4 * D); }
-
-void den_loop_io(float* ws, int rows, float** x, float** xs) {
-    *x = ws;                                   // P[0]
-    *xs = ws + (size_t)8 * rows * D;           // Ps[0]: after P[0..3] and SK[0..3]
-}
-
 static KrArgs kr(const float* A, int lda, const float* W, const float* b, float* Y, int ldy, int M, int N, int K, int act = ACT_NONE) {
     KrArgs g;
     g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
@@ -301,20 +265,14 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
     const int M = b_n * T;
     if (T < 1 || T > LADIFF_MAX_LATENTS || b_lo < 0 || b_lo + b_n > B2) return LADIFF_ERR_SHAPE;
     if (M == 0) return 0;
-    if (ws_floats < den_forward_ws_floats(b_n, T)) return LADIFF_ERR_WORKSPACE;
+    DenForwardWs a = den_forward_layout(ws, (size_t)M);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     eps += (size_t)b_lo * T * D;
     const bool sp = wsp != nullptr;
     const size_t MD = (size_t)M * D;
-    float* P[4]; float* SK[NSKIP]; float* Ps[4]; float* SKs[NSKIP];
-    float* p = ws;
-    for (int i = 0; i < 4; ++i) { P[i] = p; p += MD; }
-    for (int i = 0; i < NSKIP; ++i) { SK[i] = p; p += MD; }
-    for (int i = 0; i < 4; ++i) { Ps[i] = sp ? p : nullptr; p += MD; }          // S-format twins
-    for (int i = 0; i < NSKIP; ++i) { SKs[i] = sp ? p : nullptr; p += MD; }
-    float* qkv = p; p += 3 * MD;
-    float* att = p; p += MD;
-    float* hid = p; p += (size_t)M * FF;
-    float* part = p;                                  // split-K partial planes [4][M][256]
+    if (!sp) { for (float*& t : a.Ps) t = nullptr; for (float*& t : a.SKs) t = nullptr; }      // fp32 mode: no S-format twins
+    float *const *P = a.P, *const *SK = a.SK, *const *Ps = a.Ps, *const *SKs = a.SKs;
+    float *qkv = a.qkv, *att = a.att, *hid = a.hid, *part = a.part;
     const float* tkv = den_cache_tkv(cache, B2, ntxt);
     const float* ctab = den_cache_ctab(cache, B2, ntxt);               // ntxt > 1: the [9][B2][4][64][64] key^T value matrices
     const int R = B2 + 1;

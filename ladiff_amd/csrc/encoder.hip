@@ -14,37 +14,21 @@ static GemmArgs lin(const float* A, int lda, const float* W, const float* bias, 
     return g;
 }
 
-static int pad32(int c) { return (c + 31) / 32 * 32; }
-
-size_t enc_ws_floats(int B, int F, int T, int C) {
-    const size_t M = (size_t)B * (2 * T + F), Cp = pad32(C);
-    return M * (16 * D + 3 * D + D + FF) + (size_t)B * F * Cp + (size_t)D * Cp + (size_t)B * F * D + (size_t)B * 8 + 64;
-}
-
 int vae_encode(const EncoderW& w, const EncoderW* wsp, const float* features, const int32_t* lengths, const int32_t* counts,
                const float* eps, int B, int F, int T, int C, float* mu, float* sd, float* latent, float* ws,
                size_t ws_floats, hipStream_t s) {
     const int S = 2 * T + F;
     if (F < 1 || S > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;
-    if (ws_floats < enc_ws_floats(B, F, T, C)) return LADIFF_ERR_WORKSPACE;
+    EncWs a = enc_layout(ws, B, F, T, C);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     const int M = B * S;
     if (B == 0) return 0;
     const bool sp = wsp != nullptr;
-    const size_t MD = (size_t)M * D;
     const int Cp = pad32(C);
-    float* P[4]; float* SK[NSKIP]; float* Ps[4]; float* SKs[NSKIP];
-    float* p = ws;
-    for (int i = 0; i < 4; ++i) { P[i] = p; p += MD; }
-    for (int i = 0; i < NSKIP; ++i) { SK[i] = p; p += MD; }
-    for (int i = 0; i < 4; ++i) { Ps[i] = sp ? p : nullptr; p += MD; }
-    for (int i = 0; i < NSKIP; ++i) { SKs[i] = sp ? p : nullptr; p += MD; }
-    float* qkv = p; p += 3 * MD;
-    float* att = p; p += MD;
-    float* hid = p; p += (size_t)M * FF;
-    float* featp = p; p += (size_t)B * F * Cp;
-    float* wskel = p; p += (size_t)D * Cp;
-    float* emb = p; p += (size_t)B * F * D;
-    uint32_t* keybits = reinterpret_cast<uint32_t*>(p);
+    if (!sp) { for (float*& t : a.Ps) t = nullptr; for (float*& t : a.SKs) t = nullptr; }      // fp32 mode: no S-format twins
+    float *const *P = a.P, *const *SK = a.SK, *const *Ps = a.Ps, *const *SKs = a.SKs;
+    float *qkv = a.qkv, *att = a.att, *hid = a.hid, *featp = a.featp, *wskel = a.wskel, *emb = a.emb;
+    uint32_t* keybits = a.keybits;
 
     auto gemm_ln = [&](const float* A, int K, const float* W, const float* Wsp, const float* bias, const float* res,
                        const NormW& n1, const NormW* n2, float* dst, float* dsts) -> int {

@@ -20,8 +20,6 @@ namespace ladiff {
 
 namespace {
 
-int pad32(int c) { return (c + 31) / 32 * 32; }
-
 // A[(b, t), c * 4 + k] = x[b, 2 t - 1 + k, c] (0 outside the sequence), columns >= 4 C zero;  x rows have `ldx` floats
 __global__ __launch_bounds__(256) void im2col_k4s2_kernel(const float* __restrict__ x, int Tin, int ldx, int C, int Tout, int Kp,
                                                           size_t n, float* __restrict__ A) {
@@ -104,21 +102,14 @@ GemmArgs lin(const float* A, int lda, const float* W, int ldw, const float* bias
 }
 
 // bidirectional GRU over [B, T, Hs] inputs with per-sample lengths, then the co-embedding head; returns [B, out]
-// ws: gi [2][B][T][3H], gh [2][B][3H], h [2][B][H], cat [B][2H], hid [B][H]
+// ws: gru_head_layout (workspace.h)
 struct GruW { const float *w_ih, *w_hh, *b_ih, *b_hh, *w_ih_r, *w_hh_r, *b_ih_r, *b_hh_r; };
 struct HeadW { LinearW l0; NormW norm; LinearW l3; };
 
-size_t gru_head_floats(int B, int T, int Hs) {
-    return (size_t)2 * B * T * 3 * Hs + (size_t)2 * B * 3 * Hs + (size_t)2 * B * Hs + (size_t)B * 2 * Hs + (size_t)2 * B * Hs + 64;
-}
-
 int gru_head(const float* emb, const int32_t* lens, const GruW& gw, const float* hidden, const HeadW& hw, int B, int T, int Hs,
              int out_dim, float* out, float* ws, hipStream_t s) {
-    float* gi = ws;
-    float* gh = gi + (size_t)2 * B * T * 3 * Hs;
-    float* h = gh + (size_t)2 * B * 3 * Hs;
-    float* cat = h + (size_t)2 * B * Hs;
-    float* hid = cat + (size_t)B * 2 * Hs;
+    const GruHeadWs a = gru_head_layout(ws, B, T, Hs);
+    float *gi = a.gi, *gh = a.gh, *h = a.h, *cat = a.cat, *hid = a.hid, *hidn = a.hidn;
     const int H3 = 3 * Hs;
     // input projections of every step, both directions
     LADIFF_TRY(launch_gemm(lin(emb, Hs, gw.w_ih, Hs, gw.b_ih, gi, H3, B * T, H3, Hs), s));
@@ -136,9 +127,9 @@ int gru_head(const float* emb, const int32_t* lens, const GruW& gw, const float*
     LADIFF_LAUNCH_CHECK();
     // output_net: Linear(2H, H), LayerNorm(H), LeakyReLU(0.2), Linear(H, out)
     LADIFF_TRY(launch_gemm(lin(cat, 2 * Hs, hw.l0.w, 2 * Hs, hw.l0.b, hid, Hs, B, Hs, 2 * Hs), s));
-    hipLaunchKernelGGL(ln_lrelu_kernel, dim3((B + 3) / 4), dim3(256), 0, s, hid, hw.norm.g, hw.norm.b, Hs, B, hid + (size_t)B * Hs);
+    hipLaunchKernelGGL(ln_lrelu_kernel, dim3((B + 3) / 4), dim3(256), 0, s, hid, hw.norm.g, hw.norm.b, Hs, B, hidn);
     LADIFF_LAUNCH_CHECK();
-    return launch_gemm(lin(hid + (size_t)B * Hs, Hs, hw.l3.w, Hs, hw.l3.b, out, out_dim, B, out_dim, Hs), s);
+    return launch_gemm(lin(hidn, Hs, hw.l3.w, Hs, hw.l3.b, out, out_dim, B, out_dim, Hs), s);
 }
 
 }  // namespace
@@ -182,27 +173,19 @@ const std::vector<std::string>& t2m_text_param_names() {
 static_assert(sizeof(T2mMoveW) == 6 * sizeof(void*) && sizeof(T2mGruW) == 17 * sizeof(void*) && sizeof(T2mTextW) == 19 * sizeof(void*),
               "tables are plain pointer arrays in name order");
 
-constexpr int MOVE_H = 512, MOTION_H = 1024, TEXT_H = 512, COEMB = 512, WORD = 300, POS = 15;
+constexpr int MOVE_H = T2M_MOVE_H, MOTION_H = T2M_MOTION_H, TEXT_H = T2M_TEXT_H, WORD = T2M_WORD, POS = T2M_POS;      // workspace.h
+constexpr int COEMB = 512;
 
 // ------------------------------------------------------------------ movement encoder
-size_t t2m_move_ws_floats(int B, int F, int Cin) {
-    const int T1 = F / 2, T2 = T1 / 2;
-    const int K1 = pad32(4 * Cin);
-    return (size_t)B * T1 * K1 + (size_t)MOVE_H * K1 + (size_t)B * T1 * MOVE_H + (size_t)B * T2 * 4 * MOVE_H + (size_t)B * T2 * MOVE_H + 64;
-}
-
 int t2m_movement_encode(const float* const* w, const float* feats, int ld, int B, int F, int Cin, float* out, float* ws,
                         size_t ws_floats, hipStream_t s) {
     T2mMoveW W; std::memcpy(&W, w, sizeof(W));
     if (Cin < 1 || ld < Cin || F < 4) return LADIFF_ERR_SHAPE;        // two k4 s2 p1 convolutions: F -> F / 2 -> F / 4 frames
-    if (ws_floats < t2m_move_ws_floats(B, F, Cin)) return LADIFF_ERR_WORKSPACE;
+    const T2mMoveWs a = t2m_move_layout(ws, B, F, Cin);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     if (B == 0) return 0;
     const int T1 = F / 2, T2 = T1 / 2, K1 = pad32(4 * Cin), K2 = 4 * MOVE_H;
-    float* a1 = ws;                                   // [B*T1, K1]
-    float* w1 = a1 + (size_t)B * T1 * K1;             // conv0 weight padded to K1 columns
-    float* y1 = w1 + (size_t)MOVE_H * K1;             // [B*T1, 512]
-    float* a2 = y1 + (size_t)B * T1 * MOVE_H;         // [B*T2, 2048]
-    float* y2 = a2 + (size_t)B * T2 * K2;             // [B*T2, 512]
+    float *a1 = a.a1, *w1 = a.w1, *y1 = a.y1, *a2 = a.a2, *y2 = a.y2;
     size_t n = (size_t)B * T1 * K1;
     hipLaunchKernelGGL(im2col_k4s2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, feats, F, ld, Cin, T1, K1, n, a1);
     LADIFF_LAUNCH_CHECK();
@@ -216,39 +199,28 @@ int t2m_movement_encode(const float* const* w, const float* feats, int ld, int B
 }
 
 // ------------------------------------------------------------------ motion encoder
-size_t t2m_motion_ws_floats(int B, int T) { return (size_t)B * T * MOTION_H + gru_head_floats(B, T, MOTION_H); }
-
 int t2m_motion_encode(const float* const* w, const float* mov, const int32_t* m_lens, int B, int T, float* out, float* ws,
                       size_t ws_floats, hipStream_t s) {
     T2mGruW W; std::memcpy(&W, w, sizeof(W));
     if (T < 1) return LADIFF_ERR_SHAPE;
-    if (ws_floats < t2m_motion_ws_floats(B, T)) return LADIFF_ERR_WORKSPACE;
+    const T2mMotionWs a = t2m_motion_layout(ws, B, T);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     if (B == 0) return 0;
-    float* emb = ws;
+    float* emb = a.emb;
     LADIFF_TRY(launch_gemm(lin(mov, MOVE_H, W.input_emb.w, MOVE_H, W.input_emb.b, emb, MOTION_H, B * T, MOTION_H, MOVE_H), s));
-    return gru_head(emb, m_lens, W.gru, W.hidden, W.head, B, T, MOTION_H, COEMB, out, emb + (size_t)B * T * MOTION_H, s);
+    return gru_head(emb, m_lens, W.gru, W.hidden, W.head, B, T, MOTION_H, COEMB, out, a.gru, s);
 }
 
 // ------------------------------------------------------------------ text encoder
-size_t t2m_text_ws_floats(int B, int L) {
-    const int Kp = pad32(POS), Kw = pad32(WORD);
-    return (size_t)B * L * Kp + (size_t)WORD * Kp + (size_t)B * L * Kw + (size_t)TEXT_H * Kw + (size_t)B * L * Kw + (size_t)B * L * TEXT_H +
-           gru_head_floats(B, L, TEXT_H);
-}
-
 int t2m_text_encode(const float* const* w, const float* word_embs, const float* pos_onehot, const int32_t* cap_lens, int B, int L,
                     float* out, float* ws, size_t ws_floats, hipStream_t s) {
     T2mTextW W; std::memcpy(&W, w, sizeof(W));
     if (L < 1) return LADIFF_ERR_SHAPE;
-    if (ws_floats < t2m_text_ws_floats(B, L)) return LADIFF_ERR_WORKSPACE;
+    const T2mTextWs a = t2m_text_layout(ws, B, L);
+    if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     if (B == 0) return 0;
     const int Kp = pad32(POS), Kw = pad32(WORD), M = B * L;
-    float* posp = ws;                                 // [M, Kp]
-    float* wpos = posp + (size_t)M * Kp;              // pos_emb.weight padded [300, Kp]
-    float* wordp = wpos + (size_t)WORD * Kp;          // word_embs padded [M, Kw] (residual of the pos GEMM)
-    float* winp = wordp + (size_t)M * Kw;             // input_emb.weight padded [512, Kw]
-    float* inp = winp + (size_t)TEXT_H * Kw;          // word_embs + pos_emb(pos_onehot), [M, Kw] (columns >= 300 zero)
-    float* emb = inp + (size_t)M * Kw;                // [M, 512]
+    float *posp = a.posp, *wpos = a.wpos, *wordp = a.wordp, *winp = a.winp, *inp = a.inp, *emb = a.emb;      // inp: columns >= 300 zero
     LADIFF_TRY(launch_pad_cols(pos_onehot, posp, M, POS, Kp, s));
     LADIFF_TRY(launch_pad_cols(W.pos_emb.w, wpos, WORD, POS, Kp, s));
     LADIFF_TRY(launch_pad_cols(word_embs, wordp, M, WORD, Kw, s));
@@ -260,7 +232,7 @@ int t2m_text_encode(const float* const* w, const float* word_embs, const float* 
         LADIFF_TRY(launch_gemm(g, s));
     }
     LADIFF_TRY(launch_gemm(lin(inp, Kw, winp, Kw, W.input_emb.b, emb, TEXT_H, M, TEXT_H, Kw), s));
-    return gru_head(emb, cap_lens, W.gru, W.hidden, W.head, B, L, TEXT_H, COEMB, out, emb + (size_t)M * TEXT_H, s);
+    return gru_head(emb, cap_lens, W.gru, W.hidden, W.head, B, L, TEXT_H, COEMB, out, a.gru, s);
 }
 
 }  // namespace ladiff

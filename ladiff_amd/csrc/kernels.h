@@ -67,7 +67,6 @@ int launch_denoiser_self_attention_general(const float* qkv, const float* text_k
 
 // dec_cross.hip: the decoder's cross-attention block (q projection, attention over <= 8 memory tokens, out projection,
 // residual, norm2) as a per-sample low-rank map
-size_t dec_cross_ws_floats(int B, int T);
 int launch_decoder_cross_prep(const DecCrossPrepBatch& pb, int n, int B, int T, hipStream_t s);
 // g1 / b1 (optional): x holds pre-norm1 rows and the kernel applies LayerNorm(g1, b1) to each row as it loads it
 int launch_decoder_out_cross(const float* att_s, const float* x0, const float* wo_s, const float* bo, const float* g1, const float* b1,

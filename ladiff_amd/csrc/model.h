@@ -1,4 +1,5 @@
-// Host-side sequencing entry points shared by denoiser.hip / decoder.hip / api.hip.
+// Host-side sequencing entry points shared by denoiser.hip / decoder.hip / api.hip.  Where each entry's workspace regions lie, and the
+// size queries (*_ws_floats, *_floats, den_cache_*, den_loop_io, carve_reverse), is workspace.h's: one layout per workspace.
 #pragma once
 #include <atomic>
 #include "gemm.h"
@@ -6,20 +7,10 @@
 #include "kernels.h"
 #include "systolic_plan.h"
 #include "weights.h"
+#include "workspace.h"
 
 namespace ladiff {
 
-// time-table layout: tables[step][layer][1536] = { ca scale|shift (512), ffn scale|shift (512), time-token K|V (512) }
-constexpr int DEN_OFF_CA_MOD = 0;
-constexpr int DEN_OFF_FFN_MOD = 2 * D;
-constexpr int DEN_OFF_TIME_KV = 4 * D;
-constexpr int DEN_LAYER_STRIDE = 6 * D;
-constexpr int DEN_STEP_STRIDE = NL * DEN_LAYER_STRIDE;
-
-size_t den_tables_floats(int n_steps);
-size_t den_text_cache_floats(int B2, int n_steps, int ntxt = 1);
-size_t den_text_ws_floats(int B2, int n_steps, int ntxt = 1);
-size_t den_forward_ws_floats(int B2, int T);
 int denoiser_time_tables(const DenoiserW& w, const float* sinus, int n, float* tables, float* ws, size_t ws_floats, hipStream_t s);
 int denoiser_text_cache(const DenoiserW& w, const float* text, int B2, const float* tables, int n_steps, float* cache,
                         float* ws, size_t ws_floats, hipStream_t s, int ntxt = 1);
@@ -28,15 +19,11 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* w_split, const float* 
                      size_t ws_floats, hipStream_t s, int b_lo = 0, int b_n = -1, int loop_mode = 0, int ntxt = 1,
                      const int32_t* d_base = nullptr);
 // n_steps = steps the c table inside `cache` covers; d_base (or NULL = 0) holds the step its first row belongs to
-const float* den_cache_tkv(const float* cache, int B2, int ntxt);
-const float* den_cache_ctab(const float* cache, int B2, int ntxt);
 int denoiser_text_static(const DenoiserW& w, const float* text, int B2, float* cache, float* ws, size_t ws_floats, hipStream_t s);
 int denoiser_ctab(const DenoiserW& w, const float* tables_lo, int n, float* cache, int B2, float* u, size_t u_floats, hipStream_t s,
                   const DenoiserW* w_split = nullptr);
 int linear_cross_attention(const DenoiserW& w, int layer, const float* x, const float* xf, const float* emb, const int32_t* counts,
                            int B, int T, int N, float* out, float* ws, size_t ws_floats, hipStream_t s);
-size_t linear_cross_attention_ws_floats(int B, int T, int N);
-void den_loop_io(float* ws, int rows, float** x, float** xs);
 
 // Measurement switches (include/ladiff_hip.h, ladiff_debug_set_*): process-wide atomics.  Every value they accept selects a launch
 // form that the tests hold to the same tolerances; the timing builds that produce garbage exist in the diagnostic twin only
@@ -56,7 +43,6 @@ int dec_mlp_prepare();           // per-device kernel attributes (dynamic LDS): 
 int dec_qkv_attn_prepare();
 int dec_cross_prepare();
 int dec_mlp_min_rows();
-size_t dec_ws_floats(int B, size_t rows, int T);
 int vae_decode(const DecoderW& w, const DecoderW* w_split, const float* z, const int32_t* lengths, const int32_t* counts,
                const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s);
 
@@ -64,7 +50,6 @@ int vae_decode(const DecoderW& w, const DecoderW* w_split, const float* z, const
 int launch_dec_mlp(const float* xs, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3,
                    const float* be3, const float* g4, const float* be4, float* y, float* ys, int M, hipStream_t s);
 
-size_t enc_ws_floats(int B, int F, int T, int C);
 int vae_encode(const EncoderW& w, const EncoderW* w_split, const float* features, const int32_t* lengths,
                const int32_t* counts, const float* eps, int B, int F, int T, int C, float* mu, float* sd, float* latent, float* ws,
                size_t ws_floats, hipStream_t s);
@@ -91,8 +76,6 @@ int launch_qkv_attention(const float* x, const float* w, const float* bias, cons
                          int kv_off, int step_stride, const int32_t* d_step, const int32_t* counts, int Bs, int b_off,
                          int b_n, int T, float* out, hipStream_t s);
 
-size_t clip_ws_floats(int B, int L);
-size_t clip_ws_floats_rows(int B, int total_rows);
 int clip_text_encode(const ClipW& w, const ClipW* w_split, int n_layers, int vocab, const int64_t* ids, int B, int S, int L,
                      float* out, float* ws, size_t ws_floats, hipStream_t s, const int32_t* seq_len = nullptr,
                      const int32_t* row_off = nullptr, const int32_t* row_seq = nullptr, int total_rows = 0);
@@ -101,9 +84,6 @@ int clip_text_encode(const ClipW& w, const ClipW* w_split, int n_layers, int voc
 const std::vector<std::string>& t2m_move_param_names();
 const std::vector<std::string>& t2m_motion_param_names();
 const std::vector<std::string>& t2m_text_param_names();
-size_t t2m_move_ws_floats(int B, int F, int Cin);
-size_t t2m_motion_ws_floats(int B, int T);
-size_t t2m_text_ws_floats(int B, int L);
 int t2m_movement_encode(const float* const* w, const float* feats, int ld, int B, int F, int Cin, float* out, float* ws,
                         size_t ws_floats, hipStream_t s);
 int t2m_motion_encode(const float* const* w, const float* mov, const int32_t* m_lens, int B, int T, float* out, float* ws,

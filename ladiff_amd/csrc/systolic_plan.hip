@@ -8,10 +8,6 @@
 
 namespace ladiff {
 
-namespace {
-constexpr int D = LADIFF_LATENT_DIM, H = LADIFF_NUM_HEADS;   // common.h's D and H (that header is device code; systolic.hip checks they agree)
-}
-
 int plan_nwg(int MR) {
     const RedPlan rp = red_plan(MR);
     return NL * (4 + rp.out_groups + NSLICE + rp.red2_parts + NSLICE + rp.styl_parts * rp.styl_groups) + 2 * NSKIP + NTAIL;

@@ -9,6 +9,9 @@
 
 namespace ladiff {
 
+constexpr int D = LADIFF_LATENT_DIM;        // latent / model width      (config_ladiff_humanml3d.yaml:132 latent_dim[-1])
+constexpr int H = LADIFF_NUM_HEADS;         // heads                     (configs/modules/denoiser.yaml:7)
+constexpr int DH = D / H;                   // head dim
 constexpr int NL = LADIFF_NUM_LAYERS;        // 9 = 4 input + middle + 4 output blocks (cross_attention.py:29-33)
 constexpr int NSKIP = (NL - 1) / 2;
 constexpr int FF = LADIFF_FF_SIZE;

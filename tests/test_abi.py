@@ -141,7 +141,7 @@ def test_workspace_queries_are_monotonic(lib):
 
 def test_reverse_workspace_query_is_monotonic_in_steps(lib):
     """The step axis of ladiff_reverse_workspace_bytes over EVERY n up to 1100 at a few batches (test_workspace_queries_are_monotonic has
-    n in {1, 5, 50, 64, 65, 1000} at every batch).  The hoisted cross-attention table is held for one window of steps (csrc/api.hip reverse_window).  A schedule longer than 64
+    n in {1, 5, 50, 64, 65, 1000} at every batch).  The hoisted cross-attention table is held for one window of steps (csrc/workspace.h reverse_window).  A schedule longer than 64
     steps without a divisor that is a multiple of 10 used to keep ALL its steps resident, so 65 steps asked for more than 1000:
     ladiff_reverse_workspace_bytes(300, 1, 65, 1) = 897,876,224 bytes against 783,413,504.  Now no window exceeds 64 steps and the carve
     reserves min(n, 64) steps of table whatever the window, so every term of the query is non-decreasing in n."""

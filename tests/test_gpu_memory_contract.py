@@ -399,7 +399,7 @@ def test_reverse_with_fresh_sampler_70_step_ddpm(denoiser, precision, loop):
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 @pytest.mark.parametrize("n", [65, 67])
 def test_reverse_with_fresh_sampler_odd_windows(denoiser, precision, loop, n):
-    """B = 3, DDPM schedules above 64 steps that have no divisor that is a multiple of 10 (csrc/api.hip reverse_window): 65 steps run as 5
+    """B = 3, DDPM schedules above 64 steps that have no divisor that is a multiple of 10 (csrc/workspace.h reverse_window): 65 steps run as 5
     windows of 13 and the prime 67 as 67 windows of 1 - odd windows, step graphs that hold one step, the c table rebuilt for 13 steps or
     one, the pipeline kernel relaunched at an odd first step - inside a workspace that reserves 64 steps of table.  Tolerance as
     test_reverse_with_fresh_sampler_70_step_ddpm."""
