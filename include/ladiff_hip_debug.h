@@ -68,7 +68,7 @@ LADIFF_API int ladiff_debug_set_mlp_variant(int v);
  * request the next block's rows early in launches of >= look_ahead_from blocks; the LIN / FFN workgroups rest after every block in
  * launches of <= small_upto blocks.  -1 keeps the built-in value.  Same results. */
 LADIFF_API int ladiff_debug_set_loop_thresholds(int look_ahead_from, int small_upto);
-/* The graph re-instantiation rule, process-wide - samplers AND decode graphs (csrc/api.hip: an older graph exec is never replayed after a newer instantiation):
+/* The graph re-instantiation rule, process-wide - samplers AND decode graphs (csrc/graph_cache.h: an older graph exec is never replayed after a newer instantiation):
  * 1 (default) on, 0 off - tests/test_gpu_stress.py replays old execs on purpose. */
 LADIFF_API int ladiff_debug_set_graph_epoch_rule(int on);
 /* Number of hipGraph instantiations the process has made so far (prologue + step graphs of all samplers): tests assert that a repeated

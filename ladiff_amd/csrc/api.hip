@@ -1,13 +1,11 @@
 // extern "C" surface of libladiff_hip.so (declared in include/ladiff_hip.h).
 #include <algorithm>
 #include <cstdlib>
-#include <atomic>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "model.h"
+#include "sampler.h"
 #include "../../include/ladiff_hip_debug.h"
 
 using namespace ladiff;
@@ -16,92 +14,19 @@ namespace {
 
 inline hipStream_t S(ladiff_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+bool all_set(const float* const* w, size_t n) {
+    if (w == nullptr) return false;
+    for (size_t i = 0; i < n; ++i)
+        if (w[i] == nullptr) return false;
+    return true;
+}
 template <class W>
 bool load_weights(W& dst, const float* const* ptrs) {
-    constexpr int n = sizeof(W) / sizeof(const float*);
-    if (ptrs == nullptr) return false;
-    for (int i = 0; i < n; ++i)
-        if (ptrs[i] == nullptr) return false;
+    if (!all_set(ptrs, sizeof(W) / sizeof(const float*))) return false;
     std::memcpy(&dst, ptrs, sizeof(W));
     return true;
 }
-
-struct Sampler {
-    hipGraphExec_t exec = nullptr;
-    hipGraphExec_t setup = nullptr;       // per-call prologue (text cache, initial latents, counter reset, first network input)
-    int unroll = 1;                       // denoiser steps captured per graph launch
-    int loop_mode = 1;                    // 1: pick per call, 2: 16-row length-aware blocks, 3: 32-row blocks
-    std::vector<unsigned char> blocks;    // host copy of the block descriptors last uploaded (geometry of the previous call)
-    int plan_mr = 0, plan_nb = 0;
-    int loop = 1;                         // 1: persistent pipeline kernel when the call qualifies (systolic.hip), 0: launch per stage
-    std::vector<unsigned char> stages;    // host copy of the pipeline's stage table (source of the upload)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // bracket the N-step loop (pipeline kernel or graph replays) of the last call
-    bool time_windows = false;            // measurement aid: one event pair per window of the schedule (ladiff_sampler_set_window_timing)
-    std::vector<hipEvent_t> wev;          // [2 i], [2 i + 1]: around the loop launches of window i of the last call
-    int n_windows = 0;
-    int last_pipeline = 0;                // the last call ran the persistent pipeline kernel (1) or launch-per-stage graphs (0)
-    // fault injection for the abort-path tests (ladiff_sampler_set_fault): THIS sampler's pipeline launches lose one workgroup right after
-    // the start-up handshake and bound their waits; -1 / 0 = none / the default bound.  A field of the handle, not of the process.
-    int fault_wg = -1;
-    unsigned long long timeout_ticks = 0;
-    // per-step noise drawn on the device (ladiff_sampler_set_noise_generator): used by the calls that pass step_noise = NULL
-    NoiseGen gen = NoiseGen{0u, 0u, 0u, 0};
-    // capture key: a graph bakes pointers, shapes and scalars into its kernel nodes.  The weight tables are identified by
-    // a hash over EVERY pointer of both tables plus the caller's generation id (bumped whenever a table is rebuilt), not
-    // by the address of the host array (which a rebuilt table can land on again).
-    const void* key_ptrs[9] = {nullptr};
-    int key_ints[4] = {0};
-    unsigned key_gen_noise[4] = {0u, 0u, 0u, 0u};
-    float key_f[2] = {0.f, 0.f};
-    uint64_t key_hash = 0, key_gen = 0;
-    uint64_t epoch = 0;                   // g_graph_epoch when these graphs were instantiated (see there)
-    std::vector<hipGraphExec_t> retired;  // replaced while a launch of them could still be queued: destroyed at the next drain
-    // Graphs are CAPTURED on a stream of the handle's own and replayed on the caller's (round 5).  While a stream captures, a
-    // hipEventQuery of any event that belongs to it is refused and invalidates the capture - and torch.distributed's watchdog thread
-    // polls the end events of synchronous collectives, which run on the caller's CURRENT stream: a capture on that stream died about
-    // once in fifteen bench runs under torchrun (profiles/r5/26_*).  Nobody else holds events of this stream.
-    hipStream_t cap = nullptr;
-    int cap_dev = -1;                     // the device `cap` was created on
-};
-// The capture stream belongs to the device that was current when it was created; a handle that is later used with another device
-// current gets a new one (the old graphs hold that device's pointers and are rebuilt by their key anyway).
-static int capture_stream(hipStream_t* cap, int* cap_dev) {
-    int dev = 0;
-    LADIFF_HIP(hipGetDevice(&dev));
-    if (*cap != nullptr && *cap_dev != dev) { (void)hipStreamDestroy(*cap); *cap = nullptr; }
-    if (*cap == nullptr) { LADIFF_HIP(hipStreamCreateWithFlags(cap, hipStreamNonBlocking)); *cap_dev = dev; }
-    return 0;
-}
-
-// Graph replay and the round-3 memory fault.  Seen on ROCm 7.2 / MI355X (scripts/repro_seq.py, scripts/repro_graph.py): the graphs of one
-// sampler, replayed after two OTHER samplers had instantiated theirs and a blocking hipMemcpy had run in between, faulted at a wild
-// address (MEMORY_APERTURE_VIOLATION / an address in the host heap's range), every captured pointer still alive.  Round 4 bisected it
-// (profiles/r4/06_*): with the rule below switched off the fault reproduces every time; it goes away when the prologue graph's ONE
-// memset node (hipMemsetAsync of the 16-byte step counter) is issued outside the graph, and stays away with every KERNEL node of both
-// graphs replayed from the old execs.  So: an older exec's MEMSET NODE is what the runtime replays wrongly after newer instantiations
-// - kernel nodes (by-value argument blocks up to 3.8 KB, 300 nodes) are fine, also in a library-free program
-// (scripts/repro_graph_args.hip: clean in every configuration, the memset-node case included - the trigger needs more than that
-// program has, and was not reduced further).  Fix: NOTHING captured by this library is a memset node any more (launch_zero_fill
-// kernels: the step counter in the prologue graph, the ragged decode's output clear); tests/test_gpu_pipeline.py replays old execs on
-// purpose (LADIFF_GRAPH_EPOCH_OFF) and gets identical bits.  The rule stays as a second line, cheap (a few hundred microseconds when
-// samplers alternate): a graph is replayed only while it is the newest instantiation of THIS library; instantiations by other
-// components of the process (torch CUDA graphs, RCCL) do not count - they were never implicated (scripts/repro_graph.py 'graphs').
-std::atomic<uint64_t> g_graph_epoch{0};
-std::atomic<int> g_graph_epoch_rule{1};       // ladiff_debug_set_graph_epoch_rule
-std::atomic<int> g_graph_instantiations{0};   // ladiff_debug_graph_instantiations
-
-void drain_retired(Sampler* sp) {            // call with the stream drained
-    for (hipGraphExec_t g : sp->retired) (void)hipGraphExecDestroy(g);
-    sp->retired.clear();
-}
-
-uint64_t hash_ptrs(const float* const* p, int n, uint64_t h) {            // FNV-1a over the pointer values
-    for (int i = 0; i < n; ++i) {
-        uint64_t v = reinterpret_cast<uint64_t>(p[i]);
-        for (int b = 0; b < 8; ++b) { h ^= (v >> (8 * b)) & 0xff; h *= 1099511628211ull; }
-    }
-    return h;
-}
+const char* name_at(const std::vector<std::string>& n, int i) { return (i >= 0 && i < (int)n.size()) ? n[i].c_str() : nullptr; }
 
 }  // namespace
 
@@ -132,15 +57,9 @@ const char* ladiff_error_string(int code) {
 }
 
 int ladiff_denoiser_num_params(void) { return DEN_NPARAMS; }
-const char* ladiff_denoiser_param_name(int i) {
-    const auto& n = denoiser_param_names();
-    return (i >= 0 && i < (int)n.size()) ? n[i].c_str() : nullptr;
-}
+const char* ladiff_denoiser_param_name(int i) { return name_at(denoiser_param_names(), i); }
 int ladiff_decoder_num_params(void) { return DEC_NPARAMS; }
-const char* ladiff_decoder_param_name(int i) {
-    const auto& n = decoder_param_names();
-    return (i >= 0 && i < (int)n.size()) ? n[i].c_str() : nullptr;
-}
+const char* ladiff_decoder_param_name(int i) { return name_at(decoder_param_names(), i); }
 
 // ------------------------------------------------------------------ unit kernels
 int ladiff_gemm(const float* A, int lda, const float* A2, int lda2, int K1, const float* W, int ldw, const float* bias,
@@ -310,20 +229,16 @@ int ladiff_sampler_destroy(void* sampler) {
     Sampler* sp = reinterpret_cast<Sampler*>(sampler);
     if (sp == nullptr) return 0;
     (void)hipDeviceSynchronize();         // a replay of these graphs may still be queued
-    drain_retired(sp);
+    sp->drain_retired();
     if (sp->exec) (void)hipGraphExecDestroy(sp->exec);
     if (sp->setup) (void)hipGraphExecDestroy(sp->setup);
     if (sp->ev0) (void)hipEventDestroy(sp->ev0);
     if (sp->ev1) (void)hipEventDestroy(sp->ev1);
     for (hipEvent_t e : sp->wev) (void)hipEventDestroy(e);
-    if (sp->cap) (void)hipStreamDestroy(sp->cap);
+    sp->cap.destroy();
     delete sp;
     return 0;
 }
-
-}  // extern "C"
-
-extern "C" {
 
 int ladiff_reverse_plan(int B, int T, const int32_t* h_counts, int masked, int loop_mode, int f16x3, int cfg, int* rows_per_block, int* n_blocks) {
     LADIFF_CHECK_ARG(B >= 1 && T >= 1 && T <= LADIFF_MAX_LATENTS && loop_mode >= 1 && loop_mode <= 3 && rows_per_block && n_blocks);
@@ -542,188 +457,16 @@ int ladiff_diffusion_reverse(void* sampler, const float* const* w, const float* 
     DenoiserW W, WS;
     LADIFF_CHECK_ARG(load_weights(W, w) && text_emb && init_noise && sinusoid && coef && z && ws && B > 0 && n_steps > 0);
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
-    const DenoiserW* WSp = w_split ? &WS : nullptr;
     if (T < 1 || T > LADIFF_MAX_LATENTS || n_text < 1) return LADIFF_ERR_SHAPE;
-    ReverseWs r = carve_reverse(ws, B, T, n_steps, n_text);
-    if (ws_bytes < r.total_bytes) return LADIFF_ERR_WORKSPACE;
-    hipStream_t s = S(stream);
-    const int dup = cfg ? 2 : 1;          // guidance: the network sees cat([latents]*2) with text [uncond | cond]  ladiff.py:472-474
-    const int B2 = dup * B;
-
-    Sampler* sp = reinterpret_cast<Sampler*>(sampler);
-    // the sampler's generator stands in for a step-noise tensor the caller did not pass (schedules without noise never look at either)
-    // A generator that is off is all zeros: its seed must not be part of any graph key (the Python loop owner draws a fresh seed per call,
-    // also for deterministic schedules - a key that changed with it re-captured ~150-node graphs on every launch-per-stage call).
-    const NoiseGen gen = (sp != nullptr && step_noise == nullptr && sp->gen.on) ? sp->gen : NoiseGen{0u, 0u, 0u, 0};
-    float *xio = nullptr, *xios = nullptr;
-    den_loop_io(r.fwd, B2 * T, &xio, &xios);
-    if (WSp == nullptr) xios = nullptr;
-
-    // hoisted, once per call: time tables for every step, text cache, initial latents, step counter, first network input.
-    // The time tables depend on (weights, schedule) only: a caller that re-runs with both unchanged in the same workspace
-    // may keep them (saves ~30 small GEMM launches per call).  The rest (~50 small launches) depends on this call's text
-    // and noise; with a sampler it is replayed as a graph so that the host does not pace the GPU through it.
-    // abort / diagnostic words of the pipeline loop: cleared once per call (they are sticky over the call's windows; every
-    // other loop form leaves them at "completed")
-    LADIFF_TRY(sys_reset_status(r.sys, s));
-    if (!reuse_time_tables) LADIFF_TRY(denoiser_time_tables(W, sinusoid, n_steps, r.tables, r.fwd, r.fwd_floats, s));
-    auto prologue = [&](hipStream_t st) -> int {
-        if (n_text > 1) LADIFF_TRY(denoiser_text_cache(W, text_emb, B2, r.tables, n_steps, r.cache, r.fwd, r.fwd_floats, st, n_text));
-        else LADIFF_TRY(denoiser_text_static(W, text_emb, B2, r.cache, r.fwd, r.fwd_floats, st));      // the c table: per window, below
-        LADIFF_TRY(launch_init_latents(init_noise, counts, init_noise_sigma, r.latents, B, T, st));
-        // [0] step index, [1] tail-kernel ticket, [2] window base.  A KERNEL, not hipMemsetAsync: this runs inside the captured prologue
-        // graph, and a memset NODE is what an older exec replayed wrongly (see g_graph_epoch)
-        LADIFF_TRY(launch_zero_fill(reinterpret_cast<float*>(r.d_step), 4, st));
-        // One step = the nine denoiser layers + ONE tail launch (final LayerNorm of the guidance branches, guidance,
-        // scheduler step, next step's network input, step counter).  The network input / last-layer output buffer of the
-        // forward workspace is primed here.
-        return launch_add_pe(r.latents, W.query_pe, B, 0, B2, T, xio, xios, st);
-    };
-    auto one_step = [&](hipStream_t st) -> int {
-        LADIFF_TRY(denoiser_forward(W, WSp, r.tables, r.d_step, r.cache, r.window, r.latents, B, dup, T, counts, r.eps, r.fwd,
-                                    r.fwd_floats, st, 0, B2, 1, n_text, r.d_step + 2));
-        return launch_step_tail(xio, xios, W.norm.g, W.norm.b, r.latents, coef, r.d_step, step_noise, W.query_pe,
-                                guidance_scale, cfg, B, T, st, gen);
-    };
-    // without guidance the pipeline runs one-branch 16-row blocks, which need the latent counts on the host (or no masking at all)
-    const bool pipeline = sp != nullptr && sp->loop == 1 && n_text == 1 && sys_supported(B, T, cfg, WSp != nullptr) &&
-                          (cfg || counts == nullptr || h_counts != nullptr);
-    // Block geometry of the pipeline for THIS call's lengths.  16-row blocks carry only the valid latent rows of each prompt
-    // (length-aware packing; needs the counts on the host), 32-row blocks the padded T rows.  A step costs the larger of (blocks x
-    // the busiest stage's time per block) and one block's trip through the 59 stages: choose_plan() picks the cheaper plan.
-    std::vector<unsigned char> plan;
-    int plan_mr = 2, plan_nb = 0;
-    if (pipeline) choose_plan(B, T, h_counts, counts != nullptr, sp->loop_mode, WSp != nullptr, plan, &plan_mr, &plan_nb, cfg != 0);
-    // c-table rows of the window that starts at step `lo` (plain launches, outside the graphs: `lo` changes per window)
-    auto open_window = [&](int lo) -> int {
-        if (n_text > 1) return 0;
-        LADIFF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(r.d_step + 2), lo, 1, s));
-        return denoiser_ctab(W, r.tables + (size_t)lo * DEN_STEP_STRIDE, r.window, r.cache, B2, r.cws, r.cws_floats, s, WSp);
-    };
-    if (sp == nullptr) {
-        LADIFF_TRY(prologue(s));
-        for (int i = 0; i < n_steps; ++i) {
-            if (i % r.window == 0) LADIFF_TRY(open_window(i));
-            LADIFF_TRY(one_step(s));
-        }
-    } else {
-        const void* kp[9] = {ws, counts, final_counts, coef, step_noise, stream, text_emb, init_noise, z};
-        const int ki[4] = {B, T, n_steps + 65536 * plan_nb, cfg + 2 * (pipeline ? plan_mr : 0) + 16 * n_text + 4096 * (WSp ? 1 : 0)};
-        const float kf[2] = {guidance_scale, init_noise_sigma};
-        const unsigned kn[4] = {gen.seed_lo, gen.seed_hi, gen.prompt0, (unsigned)gen.on};      // baked into the step graphs' tail nodes
-        uint64_t h = hash_ptrs(w, DEN_NPARAMS, 1469598103934665603ull);
-        if (w_split) h = hash_ptrs(w_split, DEN_NPARAMS, h ^ 0x9e3779b97f4a7c15ull);
-        const bool same = sp->setup && std::memcmp(kp, sp->key_ptrs, sizeof(kp)) == 0 &&
-                          std::memcmp(ki, sp->key_ints, sizeof(ki)) == 0 && std::memcmp(kf, sp->key_f, sizeof(kf)) == 0 &&
-                          (pipeline || std::memcmp(kn, sp->key_gen_noise, sizeof(kn)) == 0) &&
-                          h == sp->key_hash && weights_generation == sp->key_gen;
-        // ladiff_debug_set_graph_epoch_rule(0) (test aid): trust an older exec, as tests/test_gpu_stress.py does to show that the graphs -
-        // kernel nodes only since round 4 - replay correctly however old they are
-        const bool newest = sp->epoch == g_graph_epoch.load() || g_graph_epoch_rule.load() == 0;
-        if (!same || !newest) {
-            if (!same) {
-                // replays of the old graphs may still be queued (the host never paces the GPU): drain before destroying them
-                if (sp->exec || sp->setup || !sp->retired.empty()) LADIFF_HIP(hipStreamSynchronize(s));
-                drain_retired(sp);
-                if (sp->exec) { (void)hipGraphExecDestroy(sp->exec); sp->exec = nullptr; }
-                if (sp->setup) { (void)hipGraphExecDestroy(sp->setup); sp->setup = nullptr; }
-            } else {
-                // same key, but another sampler has instantiated since: capture again.  No drain (a chunked batch alternates two
-                // samplers launch after launch): the old graphs are set aside and destroyed at the next drain
-                if (sp->retired.size() >= 8) { LADIFF_HIP(hipStreamSynchronize(s)); drain_retired(sp); }
-                if (sp->exec) { sp->retired.push_back(sp->exec); sp->exec = nullptr; }
-                if (sp->setup) { sp->retired.push_back(sp->setup); sp->setup = nullptr; }
-            }
-            hipGraph_t graph = nullptr;
-            LADIFF_TRY(capture_stream(&sp->cap, &sp->cap_dev));
-            const hipStream_t cs = sp->cap;      // captured here, replayed on `s` (see Sampler::cap)
-            {   // prologue graph
-                LADIFF_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-                const int rc0 = prologue(cs);
-                const hipError_t e0 = hipStreamEndCapture(cs, &graph);
-                if (rc0 != 0) { if (graph) (void)hipGraphDestroy(graph); return rc0; }
-                LADIFF_HIP(e0);
-                const hipError_t i0 = hipGraphInstantiate(&sp->setup, graph, nullptr, nullptr, 0);
-                ++g_graph_instantiations;
-                (void)hipGraphDestroy(graph);
-                graph = nullptr;
-                LADIFF_HIP(i0);
-            }
-            if (pipeline && same) {
-                // only the prologue graph was renewed: the stage table in the workspace is this key's
-            } else if (pipeline) {
-                // stage table of the persistent pipeline (pointers of this call's weights and workspace): built and uploaded
-                // once per key; the host copy stays alive in the sampler until the next rebuild
-                LADIFF_TRY(sys_build_stages(W, WSp ? WS : W, r.sys, plan_mr, plan_nb, sp->stages));
-                sp->blocks.clear();            // the descriptor area moved with the layout: upload again
-                LADIFF_HIP(hipMemcpyAsync(r.sys, sp->stages.data(), sp->stages.size(), hipMemcpyHostToDevice, s));
-                LADIFF_HIP(hipStreamSynchronize(s));
-            } else {
-                LADIFF_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-                // several steps per graph launch (the step index lives in device memory): fewer ~9 us replay gaps
-                int unroll = 1;
-                for (int u = 2; u <= 10; ++u) if (r.window % u == 0) unroll = u;
-                sp->unroll = unroll;
-                int rc = 0;
-                for (int u = 0; u < unroll && rc == 0; ++u) rc = one_step(cs);
-                const hipError_t ec = hipStreamEndCapture(cs, &graph);
-                if (rc != 0) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-                LADIFF_HIP(ec);
-                const hipError_t ei = hipGraphInstantiate(&sp->exec, graph, nullptr, nullptr, 0);
-                ++g_graph_instantiations;
-                (void)hipGraphDestroy(graph);
-                LADIFF_HIP(ei);
-            }
-            std::memcpy(sp->key_ptrs, kp, sizeof(kp));
-            std::memcpy(sp->key_ints, ki, sizeof(ki));
-            std::memcpy(sp->key_f, kf, sizeof(kf));
-            std::memcpy(sp->key_gen_noise, kn, sizeof(kn));
-            sp->key_hash = h;
-            sp->key_gen = weights_generation;
-            sp->epoch = ++g_graph_epoch;
-        }
-        LADIFF_HIP(hipGraphLaunch(sp->setup, s));
-        if (sp->ev0 == nullptr) { LADIFF_HIP(hipEventCreate(&sp->ev0)); LADIFF_HIP(hipEventCreate(&sp->ev1)); }
-        if (pipeline && (plan_mr != sp->plan_mr || plan_nb != sp->plan_nb || plan != sp->blocks)) {
-            // this call's block descriptors (a few KB; the runtime stages a pageable source before it returns)
-            if (!sp->blocks.empty()) LADIFF_HIP(hipStreamSynchronize(s));      // a copy from the old buffer may still be in flight
-            sp->blocks = plan; sp->plan_mr = plan_mr; sp->plan_nb = plan_nb;
-            LADIFF_HIP(hipMemcpyAsync(r.sys + sys_blocks_offset_floats(plan_mr, plan_nb), sp->blocks.data(), sp->blocks.size(),
-                                      hipMemcpyHostToDevice, s));
-        }
-        sp->last_pipeline = pipeline ? 1 : 0;
-        sp->n_windows = 0;
-        for (int lo = 0; lo < n_steps; lo += r.window) {
-            LADIFF_TRY(open_window(lo));
-            if (lo == 0) LADIFF_HIP(hipEventRecord(sp->ev0, s));       // the loop itself: from the first step's first launch
-            const int wi = lo / r.window;
-            if (sp->time_windows) {
-                while ((int)sp->wev.size() < 2 * (wi + 1)) { hipEvent_t e; LADIFF_HIP(hipEventCreate(&e)); sp->wev.push_back(e); }
-                LADIFF_HIP(hipEventRecord(sp->wev[2 * wi], s));
-            }
-            if (pipeline) {
-                LADIFF_TRY(launch_systolic_loop(W, r.sys, r.tables, den_cache_tkv(r.cache, B2, 1), den_cache_ctab(r.cache, B2, 1), r.window,
-                                                coef, step_noise, r.latents, counts, guidance_scale, B, T, lo, r.window, WSp ? 0 : 1, plan_mr, plan_nb, s, cfg,
-                                                sp->fault_wg, sp->timeout_ticks, gen));
-            } else {
-                for (int i = 0; i < r.window / sp->unroll; ++i) LADIFF_HIP(hipGraphLaunch(sp->exec, s));
-            }
-            if (sp->time_windows) { LADIFF_HIP(hipEventRecord(sp->wev[2 * wi + 1], s)); sp->n_windows = wi + 1; }
-        }
-        LADIFF_HIP(hipEventRecord(sp->ev1, s));
-    }
-    // final zeroing of the rows past each motion's latent count: applied even when the denoiser ran unmasked
-    // (TEST_EFFICIENCY), as ladiff.py:559-566 does.  An aborted pipeline launch leaves partial latents: z is then NaN.
-    return launch_finalize_latents(r.latents, final_counts, z, B, T, s,
-                                   reinterpret_cast<const unsigned*>(r.sys + sys_status_offset_floats(B, T)));
+    return diffusion_reverse(reinterpret_cast<Sampler*>(sampler), W, w_split ? &WS : nullptr,
+                             ReverseArgs{w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid, coef,
+                                         step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
+                                         reuse_time_tables, stream});
 }
 
 // ------------------------------------------------------------------ LA-VAE encoder
 int ladiff_encoder_num_params(void) { return ENC_NPARAMS; }
-const char* ladiff_encoder_param_name(int i) {
-    const auto& n = encoder_param_names();
-    return (i >= 0 && i < (int)n.size()) ? n[i].c_str() : nullptr;
-}
+const char* ladiff_encoder_param_name(int i) { return name_at(encoder_param_names(), i); }
 size_t ladiff_encoder_workspace_bytes(int B, int F, int T, int C) { return enc_ws_floats(B, F, T, C) * sizeof(float); }
 
 int ladiff_vae_encode(const float* const* w, const float* const* w_split, const float* features, const int32_t* lengths,
@@ -738,10 +481,7 @@ int ladiff_vae_encode(const float* const* w, const float* const* w_split, const 
 
 // ------------------------------------------------------------------ CLIP text encoder
 int ladiff_clip_num_params(void) { return CLIP_NPARAMS; }
-const char* ladiff_clip_param_name(int i) {
-    const auto& n = clip_param_names();
-    return (i >= 0 && i < (int)n.size()) ? n[i].c_str() : nullptr;
-}
+const char* ladiff_clip_param_name(int i) { return name_at(clip_param_names(), i); }
 size_t ladiff_clip_workspace_bytes(int B, int L) { return clip_ws_floats(B, L) * sizeof(float); }
 
 static bool load_clip(ClipW& dst, const float* const* ptrs, int n_layers) {     // only the first n_layers must be present
@@ -776,13 +516,6 @@ int ladiff_clip_text_encode_ragged(const float* const* w, const float* const* w_
 }
 
 // ------------------------------------------------------------------ T2M evaluator encoders
-static bool all_set(const float* const* w, size_t n) {
-    if (w == nullptr) return false;
-    for (size_t i = 0; i < n; ++i)
-        if (w[i] == nullptr) return false;
-    return true;
-}
-static const char* name_at(const std::vector<std::string>& n, int i) { return (i >= 0 && i < (int)n.size()) ? n[i].c_str() : nullptr; }
 int ladiff_t2m_movement_num_params(void) { return (int)t2m_move_param_names().size(); }
 const char* ladiff_t2m_movement_param_name(int i) { return name_at(t2m_move_param_names(), i); }
 int ladiff_t2m_motion_num_params(void) { return (int)t2m_motion_param_names().size(); }
@@ -873,12 +606,8 @@ int ladiff_vae_decode(const float* const* w, const float* const* w_split, const 
 namespace {
 struct DecodeGraph {
     hipGraphExec_t exec = nullptr;
-    hipStream_t cap = nullptr;            // captured on a stream of its own, replayed on the caller's (Sampler::cap)
-    int cap_dev = -1;
-    const void* key_ptrs[7] = {nullptr};
-    uint64_t epoch = 0;                   // g_graph_epoch at instantiation: replayed only while it is the newest graph of the process
-    int key_ints[6] = {0};
-    uint64_t key_hash = 0, key_gen = 0;
+    GraphSlot slot;                       // capture key (decode_key, graph_key.h) and epoch of `exec`
+    CaptureStream cap;
 };
 }  // namespace
 
@@ -892,7 +621,7 @@ int ladiff_decoder_graph_destroy(void* graph) {
     if (g == nullptr) return 0;
     (void)hipDeviceSynchronize();         // a replay may still be queued
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
-    if (g->cap) (void)hipStreamDestroy(g->cap);
+    g->cap.destroy();
     delete g;
     return 0;
 }
@@ -907,41 +636,21 @@ int ladiff_vae_decode_graphed(void* graph, const float* const* w, const float* c
     if (F < 1 || F > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;      // as the ragged entry
     if (ws_bytes < ladiff_decoder_workspace_bytes(B, F, T, C)) return LADIFF_ERR_WORKSPACE;
     hipStream_t s = S(stream);
-    const void* kp[7] = {z, lengths, counts, row_off, feats, ws, stream};
-    const int ki[6] = {B, F, T, C, total_rows, w_split ? 1 : 0};
-    uint64_t h = hash_ptrs(w, DEC_NPARAMS, 1469598103934665603ull);
-    if (w_split) h = hash_ptrs(w_split, DEC_NPARAMS, h ^ 0x9e3779b97f4a7c15ull);
-    // the measurement switches change the launch sequence: part of the key
-    h ^= (uint64_t)(g_dec_fused_mlp + 4 * g_dec_small_rows_path + 8 * g_dec_final_split + 16 * g_mlp_variant + 4096 * g_dec_fused_attn) * 0x100000001b3ull;
-    const bool same = dg->exec && std::memcmp(kp, dg->key_ptrs, sizeof(kp)) == 0 && std::memcmp(ki, dg->key_ints, sizeof(ki)) == 0 &&
-                      h == dg->key_hash && weights_generation == dg->key_gen &&
-                      (dg->epoch == g_graph_epoch.load() || g_graph_epoch_rule.load() == 0);     // the rule's switch is process-wide: samplers and decode graphs
-    if (!same) {
+    const GraphKey key = decode_key(w, w_split, DEC_NPARAMS, weights_generation, z, lengths, counts, row_off, total_rows, B, F, T, C, feats, ws,
+                                    stream, g_dec_fused_mlp, g_dec_small_rows_path, g_dec_final_split, g_mlp_variant, g_dec_fused_attn);
+    if (!(dg->exec && dg->slot.key == key && dg->slot.newest())) {
         if (dg->exec) { LADIFF_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(dg->exec); dg->exec = nullptr; }
         LADIFF_TRY(dec_mlp_prepare());            // kernel attributes are set outside the capture
         LADIFF_TRY(dec_qkv_attn_prepare());
         LADIFF_TRY(dec_cross_prepare());
-        hipGraph_t gr = nullptr;
-        LADIFF_TRY(capture_stream(&dg->cap, &dg->cap_dev));
-        const hipStream_t cs = dg->cap;
-        LADIFF_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        int rc = 0;
-        if (row_off != nullptr) {      // inside the capture: a zero-fill KERNEL, never a memset node (g_graph_epoch)
-            rc = launch_zero_fill(feats, (size_t)B * F * C, cs);
-        }
-        if (rc == 0) rc = vae_decode(W, w_split ? &WS : nullptr, z, lengths, counts, row_off, total_rows, B, F, T, C, feats, (float*)ws,
-                                     ws_bytes / sizeof(float), cs);
-        const hipError_t ec = hipStreamEndCapture(cs, &gr);
-        if (rc != 0) { if (gr) (void)hipGraphDestroy(gr); return rc; }
-        LADIFF_HIP(ec);
-        const hipError_t ei = hipGraphInstantiate(&dg->exec, gr, nullptr, nullptr, 0);
-        ++g_graph_instantiations;
-        (void)hipGraphDestroy(gr);
-        LADIFF_HIP(ei);
-        std::memcpy(dg->key_ptrs, kp, sizeof(kp));
-        std::memcpy(dg->key_ints, ki, sizeof(ki));
-        dg->key_hash = h; dg->key_gen = weights_generation;
-        dg->epoch = ++g_graph_epoch;
+        LADIFF_TRY(dg->cap.ensure());
+        LADIFF_TRY(capture_graph(dg->cap.s, [&](hipStream_t cs) {
+            // inside the capture: a zero-fill KERNEL, never a memset node (g_graph_epoch)
+            if (row_off != nullptr) LADIFF_TRY(launch_zero_fill(feats, (size_t)B * F * C, cs));
+            return vae_decode(W, w_split ? &WS : nullptr, z, lengths, counts, row_off, total_rows, B, F, T, C, feats, (float*)ws,
+                              ws_bytes / sizeof(float), cs);
+        }, &dg->exec));
+        dg->slot.stamp(key);
     }
     LADIFF_HIP(hipGraphLaunch(dg->exec, s));
     return 0;

@@ -1,0 +1,133 @@
+// The capture key of a hipGraph as a value.  A graph bakes pointers, shapes and scalars into its kernel nodes: it may be replayed only
+// for a call that would bake in the same ones.  A key is the list of them, every entry added by name, compared entry by entry; a new
+// input to a graph is one more add in its builder below.  Plain C++17 with no HIP header, like systolic_plan.h: tests/graph_key_check.cpp
+// runs this header on the CPU under sanitizers (tests/test_graph_key.py).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+
+namespace ladiff {
+
+struct GraphKey {
+    static constexpr int CAPACITY = 32;                  // entries; the sampler's key has 26, the decode graph's 20.  One too many aborts.
+    uint64_t v[CAPACITY] = {0};
+    int n = 0;
+
+    GraphKey& add(uint64_t x) {
+        if (n == CAPACITY) std::abort();                 // never a silently shorter key
+        v[n++] = x;
+        return *this;
+    }
+    GraphKey& add(const void* p) { return add((uint64_t) reinterpret_cast<uintptr_t>(p)); }
+    GraphKey& add(int x) { return add((uint64_t)(int64_t)x); }
+    GraphKey& add(unsigned x) { return add((uint64_t)x); }
+    GraphKey& add(float x) {                             // by bit pattern: 0.0f and -0.0f are different keys
+        uint32_t u;
+        static_assert(sizeof(u) == sizeof(x), "float is 32 bits");
+        std::memcpy(&u, &x, sizeof(u));
+        return add((uint64_t)u);
+    }
+    bool operator==(const GraphKey& o) const { return n == o.n && std::equal(v, v + n, o.v); }
+    bool operator!=(const GraphKey& o) const { return !(*this == o); }
+};
+
+// A weight table is identified by a hash over EVERY pointer of both tables plus the caller's generation id (bumped whenever a table is
+// rebuilt), not by the address of the host array (which a rebuilt table can land on again).  FNV-1a over the pointer values.
+inline uint64_t fnv1a_ptrs(const float* const* p, int n, uint64_t h) {
+    for (int i = 0; i < n; ++i) {
+        const uint64_t x = reinterpret_cast<uintptr_t>(p[i]);
+        for (int b = 0; b < 8; ++b) { h ^= (x >> (8 * b)) & 0xff; h *= 1099511628211ull; }
+    }
+    return h;
+}
+inline uint64_t weights_hash(const float* const* w, const float* const* w_split, int n) {
+    const uint64_t h = fnv1a_ptrs(w, n, 1469598103934665603ull);
+    return w_split != nullptr ? fnv1a_ptrs(w_split, n, h ^ 0x9e3779b97f4a7c15ull) : h;
+}
+
+// The parameter list of ladiff_diffusion_reverse (include/ladiff_hip.h) as a record: api.hip fills it, the sampler's key reads it here,
+// ladiff::diffusion_reverse (reverse.hip) runs it.
+struct ReverseArgs {
+    const float* const* w;
+    const float* const* w_split;
+    uint64_t weights_generation;
+    const float *text_emb, *init_noise;
+    const int32_t *counts, *final_counts, *h_counts;
+    const float *sinusoid, *coef, *step_noise;
+    float guidance_scale, init_noise_sigma;
+    int cfg, B, T, n_text, n_steps;
+    float* z;
+    void* ws;
+    size_t ws_bytes;
+    int reuse_time_tables;
+    void* stream;
+};
+
+// Key of a sampler's graphs (prologue graph + step graph, or prologue graph + the pipeline's stage table).  n_params: pointers per weight
+// table.  pipeline / plan_mr / plan_nb: the loop form of this call and its block plan (launch-per-stage: pass any plan, it is keyed as 0).
+// noise[4]: the noise generator's words {seed_lo, seed_hi, prompt0, on}, baked into the step graphs' tail nodes.  The pipeline kernel takes
+// them as launch arguments instead (nothing captured holds them), so a pipeline call keys four zeros: the loop owner draws a fresh seed per
+// call and must not capture again for it.  The zeros cannot make a pipeline key equal a launch-per-stage key with the generator off:
+// the `pipeline` and `plan_mr` entries (1 and 1 | 2 against 0 and 0) differ between any two such keys.
+inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, int plan_mr, int plan_nb, const unsigned noise[4]) {
+    GraphKey k;
+    k.add(a.ws);
+    k.add(a.counts);
+    k.add(a.final_counts);
+    k.add(a.coef);
+    k.add(a.step_noise);
+    k.add(a.stream);
+    k.add(a.text_emb);
+    k.add(a.init_noise);
+    k.add(a.z);
+    k.add(a.B);
+    k.add(a.T);
+    k.add(a.n_steps);
+    k.add(a.cfg);
+    k.add(a.n_text);
+    k.add(a.w_split != nullptr ? 1 : 0);
+    k.add(pipeline ? 1 : 0);
+    k.add(pipeline ? plan_mr : 0);
+    k.add(pipeline ? plan_nb : 0);
+    k.add(a.guidance_scale);
+    k.add(a.init_noise_sigma);
+    for (int i = 0; i < 4; ++i) k.add(pipeline ? 0u : noise[i]);
+    k.add(weights_hash(a.w, a.w_split, n_params));
+    k.add(a.weights_generation);
+    return k;
+}
+
+// Key of a decode graph (ladiff_vae_decode_graphed).  The five measurement switches change the launch sequence: part of the key.
+// (g_dec_out_cross changes it too and is NOT keyed: a known gap)
+inline GraphKey decode_key(const float* const* w, const float* const* w_split, int n_params, uint64_t weights_generation, const float* z,
+                           const int32_t* lengths, const int32_t* counts, const int32_t* row_off, int total_rows, int B, int F, int T, int C,
+                           const float* feats, const void* ws, const void* stream, int dec_fused_mlp, int dec_small_rows_path,
+                           int dec_final_split, int mlp_variant, int dec_fused_attn) {
+    GraphKey k;
+    k.add(z);
+    k.add(lengths);
+    k.add(counts);
+    k.add(row_off);
+    k.add(feats);
+    k.add(ws);
+    k.add(stream);
+    k.add(B);
+    k.add(F);
+    k.add(T);
+    k.add(C);
+    k.add(total_rows);
+    k.add(w_split != nullptr ? 1 : 0);
+    k.add(dec_fused_mlp);
+    k.add(dec_small_rows_path);
+    k.add(dec_final_split);
+    k.add(mlp_variant);
+    k.add(dec_fused_attn);
+    k.add(weights_hash(w, w_split, n_params));
+    k.add(weights_generation);
+    return k;
+}
+
+}  // namespace ladiff

@@ -1,9 +1,10 @@
-// Host-side sequencing entry points shared by denoiser.hip / decoder.hip / api.hip.  Where each entry's workspace regions lie, and the
+// Host-side sequencing entry points shared by denoiser.hip / decoder.hip / reverse.hip / api.hip.  Where each entry's workspace regions lie, and the
 // size queries (*_ws_floats, *_floats, den_cache_*, den_loop_io, carve_reverse), is workspace.h's: one layout per workspace.
 #pragma once
 #include <atomic>
 #include "gemm.h"
 #include "gemm_kr.h"
+#include "graph_key.h"
 #include "kernels.h"
 #include "systolic_plan.h"
 #include "weights.h"
@@ -24,6 +25,10 @@ int denoiser_ctab(const DenoiserW& w, const float* tables_lo, int n, float* cach
                   const DenoiserW* w_split = nullptr);
 int linear_cross_attention(const DenoiserW& w, int layer, const float* x, const float* xf, const float* emb, const int32_t* counts,
                            int B, int T, int N, float* out, float* ws, size_t ws_floats, hipStream_t s);
+
+// reverse.hip: the whole reverse loop of ladiff_diffusion_reverse (arguments checked by the caller); sp may be null (plain launches)
+struct Sampler;      // sampler.h
+int diffusion_reverse(Sampler* sp, const DenoiserW& w, const DenoiserW* w_split, const ReverseArgs& a);
 
 // Measurement switches (include/ladiff_hip.h, ladiff_debug_set_*): process-wide atomics.  Every value they accept selects a launch
 // form that the tests hold to the same tolerances; the timing builds that produce garbage exist in the diagnostic twin only

@@ -2,8 +2,8 @@
 stream, then at once a call that captures (the arithmetic mode alternates, so every call re-captures; the launch-per-stage loop, whose
 step graphs take several ms to capture), N times.  With captures on the CALLER's stream (round 5 before the fix) this died within 150
 pairs: the watchdog polls the collective's end event, which belongs to the current stream, and a hipEventQuery of an event of a
-capturing stream is refused and invalidates the capture.  The library now captures on a stream of the handle's own (csrc/api.hip,
-Sampler::cap).  usage: capture_vs_watchdog.py [pairs]"""
+capturing stream is refused and invalidates the capture.  The library now captures on a stream of the handle's own (csrc/graph_cache.h,
+CaptureStream).  usage: capture_vs_watchdog.py [pairs]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 150

@@ -1,0 +1,122 @@
+// The capture keys of the library's hipGraphs (csrc/graph_key.h) on the CPU: plain C++17, built with AddressSanitizer + UBSan by
+// tests/test_graph_key.py and run as a child process.  Prints "graph_key_check: ok" or the first failed property.
+#include <cstdio>
+#include <cstdlib>
+#include <functional>
+#include <vector>
+
+#include "graph_key.h"
+
+using namespace ladiff;
+
+#define CHECK(cond) \
+    do { if (!(cond)) { std::printf("graph_key_check: FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); std::exit(1); } } while (0)
+
+static float slab[64];                    // addresses for the pointer entries; never dereferenced
+static const float* P(int i) { return slab + i; }
+
+// one entry of every type; `change` (0 .. 4) replaces one of them
+static GraphKey mixed(int change = -1) {
+    GraphKey k;
+    k.add((const void*)P(change == 0 ? 1 : 0));
+    k.add(change == 1 ? -7 : 7);
+    k.add(change == 2 ? 0x80000001u : 0x80000000u);
+    k.add(change == 3 ? 1.5f : 0.5f);
+    k.add(change == 4 ? (uint64_t(1) << 40) + 1 : uint64_t(1) << 40);
+    return k;
+}
+
+static uint64_t fnv_restated(const std::vector<const float*>& w, const std::vector<const float*>* ws) {
+    uint64_t h = 1469598103934665603ull;
+    auto eat = [&](const std::vector<const float*>& t) {
+        for (const float* p : t)
+            for (int b = 0; b < 8; ++b) { h ^= ((uint64_t) reinterpret_cast<uintptr_t>(p) >> (8 * b)) & 0xff; h *= 1099511628211ull; }
+    };
+    eat(w);
+    if (ws) { h ^= 0x9e3779b97f4a7c15ull; eat(*ws); }
+    return h;
+}
+
+static const float* const W_TAB[3] = {slab + 10, slab + 11, slab + 12};
+static const float* const S_TAB[3] = {slab + 20, slab + 21, slab + 22};
+
+static ReverseArgs reverse_args(int n_text = 1) {
+    ReverseArgs a{};
+    a.w = W_TAB; a.w_split = S_TAB; a.weights_generation = 3;
+    a.text_emb = P(30); a.init_noise = P(31); a.sinusoid = P(32); a.coef = P(33); a.step_noise = nullptr;
+    a.guidance_scale = 7.5f; a.init_noise_sigma = 1.f;
+    a.cfg = 1; a.B = 2; a.T = 5; a.n_text = n_text; a.n_steps = 50;
+    a.z = slab + 34; a.ws = slab + 35; a.ws_bytes = 1 << 20; a.stream = slab + 36;
+    return a;
+}
+
+int main() {
+    // equality: field-wise, order-sensitive, by bit pattern
+    CHECK(mixed() == mixed() && !(mixed() != mixed()));
+    for (int c = 0; c < 5; ++c) CHECK(mixed(c) != mixed() && !(mixed(c) == mixed()));
+    CHECK(GraphKey().add(1).add(2) != GraphKey().add(2).add(1));
+    CHECK(GraphKey().add(0.0f) != GraphKey().add(-0.0f));
+    CHECK(GraphKey().add(1).add(2) != GraphKey().add(1));              // a prefix is another key
+    CHECK(GraphKey() == GraphKey() && GraphKey() != mixed() && GraphKey() != GraphKey().add(0));     // an empty key equals no filled one
+    {
+        GraphKey full;
+        for (int i = 0; i < GraphKey::CAPACITY; ++i) full.add(i);     // exactly the capacity fits (one more aborts: not run here)
+        CHECK(full.n == GraphKey::CAPACITY && full == full);
+    }
+
+    // weights_hash: FNV-1a over the pointer values of both tables
+    const std::vector<const float*> w(W_TAB, W_TAB + 3), s(S_TAB, S_TAB + 3);
+    CHECK(weights_hash(W_TAB, nullptr, 3) == fnv_restated(w, nullptr));
+    CHECK(weights_hash(W_TAB, S_TAB, 3) == fnv_restated(w, &s));
+    CHECK(weights_hash(W_TAB, S_TAB, 3) != weights_hash(W_TAB, nullptr, 3));      // split table present / absent
+    CHECK(weights_hash(W_TAB, S_TAB, 3) != weights_hash(S_TAB, W_TAB, 3));        // the two tables swapped
+    CHECK(weights_hash(W_TAB, W_TAB, 3) != weights_hash(W_TAB, nullptr, 3));
+    for (int i = 0; i < 3; ++i) {
+        const float* w2[3] = {W_TAB[0], W_TAB[1], W_TAB[2]};
+        w2[i] = slab + 40;
+        CHECK(weights_hash(w2, S_TAB, 3) != weights_hash(W_TAB, S_TAB, 3));       // one pointer of either table changed
+        CHECK(weights_hash(W_TAB, w2, 3) != weights_hash(W_TAB, S_TAB, 3));
+    }
+
+    // the sampler's key and the noise generator's words
+    const unsigned off[4] = {0u, 0u, 0u, 0u}, seed_a[4] = {11u, 12u, 0u, 1u}, seed_b[4] = {21u, 12u, 0u, 1u};
+    const ReverseArgs a = reverse_args();
+    CHECK(sampler_key(a, 3, true, 1, 6, seed_a) == sampler_key(a, 3, true, 1, 6, seed_b));       // pipeline: the seed is a launch argument
+    CHECK(sampler_key(a, 3, false, 2, 0, seed_a) != sampler_key(a, 3, false, 2, 0, seed_b));     // launch per stage: baked into the step graph
+    CHECK(sampler_key(a, 3, false, 2, 0, seed_a) == sampler_key(a, 3, false, 1, 9, seed_a));     // ... whose key ignores the unused block plan
+    for (int n_text : {1, 4, 77})
+        for (int mr : {1, 2})
+            for (int other_mr : {1, 2})
+                for (const unsigned* noise : {off, seed_a})
+                    CHECK(sampler_key(reverse_args(n_text), 3, true, mr, 6, seed_a) != sampler_key(reverse_args(n_text), 3, false, other_mr, 6, noise));
+    CHECK(sampler_key(a, 3, true, 1, 6, off) != sampler_key(a, 3, true, 2, 6, off) && sampler_key(a, 3, true, 1, 6, off) != sampler_key(a, 3, true, 1, 7, off));
+    // every argument a graph bakes in changes the key (h_counts, sinusoid, ws_bytes and reuse_time_tables are used outside the graphs)
+    const std::vector<std::function<void(ReverseArgs&)>> changes = {
+        [](ReverseArgs& x) { x.ws = slab + 50; }, [](ReverseArgs& x) { x.counts = (const int32_t*)(slab + 50); },
+        [](ReverseArgs& x) { x.final_counts = (const int32_t*)(slab + 50); }, [](ReverseArgs& x) { x.coef = P(50); },
+        [](ReverseArgs& x) { x.step_noise = P(50); }, [](ReverseArgs& x) { x.stream = slab + 50; }, [](ReverseArgs& x) { x.text_emb = P(50); },
+        [](ReverseArgs& x) { x.init_noise = P(50); }, [](ReverseArgs& x) { x.z = slab + 50; }, [](ReverseArgs& x) { x.B = 3; },
+        [](ReverseArgs& x) { x.T = 4; }, [](ReverseArgs& x) { x.n_steps = 20; }, [](ReverseArgs& x) { x.cfg = 0; }, [](ReverseArgs& x) { x.n_text = 4; },
+        [](ReverseArgs& x) { x.w_split = nullptr; }, [](ReverseArgs& x) { x.w = S_TAB; }, [](ReverseArgs& x) { x.weights_generation = 4; },
+        [](ReverseArgs& x) { x.guidance_scale = 5.f; }, [](ReverseArgs& x) { x.init_noise_sigma = -1.f; }};
+    for (bool pipeline : {false, true})
+        for (const auto& change : changes) {
+            ReverseArgs b = reverse_args();
+            change(b);
+            CHECK(sampler_key(b, 3, pipeline, 1, 6, off) != sampler_key(a, 3, pipeline, 1, 6, off));
+        }
+
+    // the decode graph's key: the five measurement switches are entries of their own
+    auto dkey = [&](int sw, int v) {
+        int q[5] = {1, 1, 1, 0, 1};
+        if (sw >= 0) q[sw] = v;
+        return decode_key(W_TAB, S_TAB, 3, 1, P(30), (const int32_t*)P(31), (const int32_t*)P(32), nullptr, 0, 2, 60, 5, 263, P(33), slab + 34,
+                          slab + 35, q[0], q[1], q[2], q[3], q[4]);
+    };
+    CHECK(dkey(-1, 0) == dkey(-1, 0));
+    for (int sw = 0; sw < 5; ++sw) CHECK(dkey(sw, 2) != dkey(-1, 0));
+    CHECK(dkey(0, 0) != dkey(1, 0));          // switches that the multiplied-up sum could have folded together stay apart
+    CHECK(dkey(-1, 0) != sampler_key(a, 3, true, 1, 6, off));
+    std::printf("graph_key_check: ok\n");
+    return 0;
+}

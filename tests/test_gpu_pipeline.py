@@ -190,7 +190,7 @@ def test_repeated_full_size_calls_are_identical(nets, precision):
 
 @pytest.mark.parametrize("precision", ["f16x3", "fp32"])
 def test_old_step_graph_is_not_replayed_after_other_plans(nets, precision):
-    """A hipGraph is replayed only while it is the newest graph instantiation of the process (api.hip, g_graph_epoch).  The sequence
+    """A hipGraph is replayed only while it is the newest graph instantiation of the process (graph_cache.h, g_graph_epoch).  The sequence
     that failed before: launch-per-stage loop at 200 prompts (its ~150-node step graph instantiated), a blocking status read, two
     other batch shapes (two more samplers, their graphs, status reads), the first shape again - the replay of the FIRST step graph
     dispatched kernels with garbage pointers (memory access fault; the same sequence without graphs was clean, every captured

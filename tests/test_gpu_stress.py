@@ -31,7 +31,7 @@ def test_random_decode_shapes():
 def test_random_loop_shapes_and_forms():
     """The reverse loop on random batches (1 ... 520 prompts, chunked batches included, with and without guidance), both arithmetic modes:
     pipeline against launch-per-stage loop, repeat identical, 16- against 32-row plan identical, status clean after every call - the run
-    that found the stale step graph (api.hip, g_graph_epoch)."""
+    that found the stale step graph (graph_cache.h, g_graph_epoch)."""
     out = _run("stress_shapes.py", 24, 7)
     assert "fp32: 24 shapes done, 0 bad so far" in out
 
@@ -45,7 +45,7 @@ def test_random_sample_sequences_on_one_object():
 
 
 def test_old_graph_execs_replay_correctly_without_the_epoch_rule():
-    """The round-3 fault, bisected in round 4 (api.hip, g_graph_epoch; profiles/r4/06_*): an OLDER exec's memset node was what the runtime
+    """The round-3 fault, bisected in round 4 (graph_cache.h, g_graph_epoch; profiles/r4/06_*): an OLDER exec's memset node was what the runtime
     replayed wrongly.  No graph of this library holds a memset node any more, so the formerly failing sequence - plan A, two other plans
     with blocking status reads in between, plan A again from its old execs - must be clean with the re-instantiation rule switched OFF."""
     env = dict(os.environ, LADIFF_GRAPH_EPOCH_OFF="1", STATUS="1")
