@@ -405,6 +405,37 @@ LADIFF_API size_t ladiff_encoder_workspace_bytes(int B, int F, int T, int C);
 LADIFF_API int ladiff_vae_encode(const float* const* w, const float* const* w_split /*or NULL*/, const float* features,
                       const int32_t* lengths, const int32_t* counts, const float* eps, int B, int F, int T, int C,
                       float* mu, float* std, float* latent, void* ws, size_t ws_bytes, ladiff_stream_t stream);
+/* The same encode with the DVAE input corruption (ablation DVAE / PERCENTAGE_NOISED; LADiffVae.add_noise, ladiff_vae.py:136-150,
+ * applied by every encode call, evaluation included: :175-176): the encoder reads
+ *   features[b][f][c] + (slot[f*C + c] >= 0 ? values[b][slot[f*C + c]] : 0)
+ * where slot is a device int32 [F*C] table (a column of values, or -1: the same positions for the whole batch, as the reference's one
+ * np.random.choice per call) and values is [B, n] (one standard normal per sample and position).  The sum is formed in the pass that
+ * brings the features into the workspace: no extra buffer, the same workspace query (ladiff_encoder_workspace_bytes), and every later
+ * kernel is ladiff_vae_encode's.  A slot outside [0, n) adds nothing; with every slot -1 the results are ladiff_vae_encode's bits.
+ * values may be NULL when n == 0. */
+LADIFF_API int ladiff_vae_encode_dvae(const float* const* w, const float* const* w_split /*or NULL*/, const float* features,
+                           const int32_t* lengths, const int32_t* counts, const float* eps, int B, int F, int T, int C,
+                           float* mu, float* std, float* latent, void* ws, size_t ws_bytes, const int32_t* slot,
+                           const float* values, int n, ladiff_stream_t stream);
+
+/* ------------------------------------------------------------------ stage-"vae" losses (csrc/vae_losses.hip)
+ * MLDLosses.update in stage "vae" (models/losses/mld.py:98-107, :141-147) on what LADIFF.train_vae_forward returns (ladiff.py:815-871):
+ *   recons_feature = mean SmoothL1(m_rst, m_ref) over [B,F,C]            (torch.nn.SmoothL1Loss, beta 1: 0.5 d^2 if |d| < 1, else |d| - 0.5)
+ *   recons_joints  = mean SmoothL1(joints_rst, joints_ref) over [B,F,J,3]
+ *   kl_motion      = mean over ALL [T,B,256] elements of 0.5 (std^2 + mu^2 - 1 - log std^2)
+ *                    (torch.distributions.kl_divergence(Normal(mu, std), Normal(0, 1)), mld.py:162-164; the rows at and beyond a
+ *                    sample's latent count are part of the reference's dist_m and are included)
+ *   total          = lambda_rec recons_feature + lambda_joint recons_joints + lambda_kl kl_motion            (mld.py:95-96, :146)
+ * batch[4] (device fp64) receives {recons_feature, recons_joints, kl_motion, total}; acc[4] (device fp64, caller-owned state: zero it to
+ * reset) gains them - the reference's `+=` per update - without a host synchronisation.  Inputs are widened to fp64 before the
+ * subtraction, sums are fp64; two launches (per-workgroup partial sums in fixed workspace slots, then one workgroup adds them in slot
+ * order), no floating-point atomics: two calls on the same inputs leave the same bits.  LADIFF_ERR_SHAPE for a size < 1 or a misaligned
+ * pointer (inputs 4 bytes; batch, acc, ws 8).  The query is non-decreasing in every argument. */
+LADIFF_API size_t ladiff_vae_losses_workspace_bytes(int B, int F, int C, int J, int T);
+LADIFF_API int ladiff_vae_losses(const float* m_rst, const float* m_ref, const float* joints_rst, const float* joints_ref,
+                      const float* mu, const float* std, int B, int F, int C, int J, int T, double lambda_rec,
+                      double lambda_joint, double lambda_kl, double* batch, double* acc, void* ws, size_t ws_bytes,
+                      ladiff_stream_t stream);
 
 /* ------------------------------------------------------------------ CLIP text encoder (the caller side)
  * MldTextEncoder.forward, mld_clip.py:51-86, "clip" branch (call sites ladiff.py:265, :1048, :1144):

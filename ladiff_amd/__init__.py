@@ -10,8 +10,9 @@ from .schedulers import DDIMScheduler, DDPMScheduler    # noqa: F401
 from .text_encoder import MldTextEncoder                # noqa: F401
 from .evaluators import (MovementConvEncoder, MotionEncoderBiGRUCo, TextEncoderBiGRUCo,   # noqa: F401
                          TM2TMetrics, MMMetrics)
-from .evaluation import evaluate, get_metric_statistics   # noqa: F401
+from .evaluation import evaluate, get_metric_statistics, validate   # noqa: F401
 from .joint_metrics import ComputeMetrics, MRMetrics, TemosMetric   # noqa: F401
+from .losses import MLDLosses   # noqa: F401
 
 __all__ = ["LADiffDenoiser", "LADiffVae", "LADIFF", "DDIMScheduler", "DDPMScheduler", "instantiate_from_config", "Feats2Joints", "MldTextEncoder", "MovementConvEncoder", "MotionEncoderBiGRUCo", "TextEncoderBiGRUCo",
-           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics"]
+           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics", "validate", "MLDLosses"]

@@ -7,7 +7,7 @@ tensor, it raises.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_size_t, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_size_t, c_uint64, c_void_p
 
 import numpy as np
 import torch
@@ -112,6 +112,11 @@ _SIGNATURES = {
     "ladiff_encoder_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "ladiff_vae_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ladiff_vae_encode_dvae": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p]),
+    "ladiff_vae_losses_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "ladiff_vae_losses": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                  c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ladiff_clip_num_params": (c_int, []),
     "ladiff_clip_param_name": (c_char_p, [c_int]),
     "ladiff_clip_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -479,6 +479,37 @@ int ladiff_vae_encode(const float* const* w, const float* const* w_split, const 
                       ws_bytes / sizeof(float), S(stream));
 }
 
+int ladiff_vae_encode_dvae(const float* const* w, const float* const* w_split, const float* features, const int32_t* lengths,
+                           const int32_t* counts, const float* eps, int B, int F, int T, int C, float* mu, float* std, float* latent,
+                           void* ws, size_t ws_bytes, const int32_t* slot, const float* values, int n, ladiff_stream_t stream) {
+    EncoderW W, WS;
+    LADIFF_CHECK_ARG(load_weights(W, w) && features && lengths && counts && eps && mu && std && latent && ws && B >= 0);
+    LADIFF_CHECK_ARG(slot && n >= 0 && (values || n == 0));
+    if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
+    if ((reinterpret_cast<uintptr_t>(slot) & 3) || (reinterpret_cast<uintptr_t>(values) & 3)) return LADIFF_ERR_SHAPE;
+    return vae_encode(W, w_split ? &WS : nullptr, features, lengths, counts, eps, B, F, T, C, mu, std, latent, (float*)ws,
+                      ws_bytes / sizeof(float), S(stream), slot, values, n);
+}
+
+// ------------------------------------------------------------------ stage-"vae" losses (csrc/vae_losses.hip)
+size_t ladiff_vae_losses_workspace_bytes(int B, int F, int C, int J, int T) { return vae_losses_ws_floats(B, F, C, J, T) * sizeof(float); }
+
+int ladiff_vae_losses(const float* m_rst, const float* m_ref, const float* joints_rst, const float* joints_ref, const float* mu,
+                      const float* std, int B, int F, int C, int J, int T, double lambda_rec, double lambda_joint, double lambda_kl,
+                      double* batch, double* acc, void* ws, size_t ws_bytes, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(m_rst && m_ref && joints_rst && joints_ref && mu && std && batch && acc && ws);
+    if (B < 1 || F < 1 || C < 1 || J < 1 || T < 1) return LADIFF_ERR_SHAPE;
+    for (const void* p : {(const void*)m_rst, (const void*)m_ref, (const void*)joints_rst, (const void*)joints_ref, (const void*)mu,
+                          (const void*)std})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return LADIFF_ERR_SHAPE;
+    for (const void* p : {(const void*)batch, (const void*)acc, (const void*)ws})
+        if (reinterpret_cast<uintptr_t>(p) & 7) return LADIFF_ERR_SHAPE;
+    const VaeLossWs a = vae_losses_layout((float*)ws, B, F, C, J, T);
+    if (ws_bytes / sizeof(float) < a.total) return LADIFF_ERR_WORKSPACE;
+    return launch_vae_losses(m_rst, m_ref, (size_t)B * F * C, joints_rst, joints_ref, (size_t)B * F * J * 3, mu, std, (size_t)T * B * D,
+                             lambda_rec, lambda_joint, lambda_kl, a.part, a.blocks, batch, acc, S(stream));
+}
+
 // ------------------------------------------------------------------ CLIP text encoder
 int ladiff_clip_num_params(void) { return CLIP_NPARAMS; }
 const char* ladiff_clip_param_name(int i) { return name_at(clip_param_names(), i); }

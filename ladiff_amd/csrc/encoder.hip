@@ -1,5 +1,5 @@
 // Host-side sequencing of the LA-VAE encoder (LADiffVae.encode, ladiff_vae.py:162-286; live branch: pe "mld", MAX_IT > 0,
-// LAD, no MLP_DIST / JOINT_DISTRO_FIX / DVAE) - SURVEY.md §8f-3, the row next to the sampling path.  It reuses the
+// LAD, no MLP_DIST / JOINT_DISTRO_FIX; DVAE as an input pass) - SURVEY.md §8f-3, the row next to the sampling path.  It reuses the
 // decoder's kernels: large-M GEMMs with fused residual + LayerNorm, the MFMA self-attention core (now with an arbitrary
 // key map: the masked latent tokens sit in the middle of the sequence), row kernels.  Sequence = [T mu tokens | T logvar
 // tokens | F frames] per sample, batch-major rows (row = b * S + s), S = 2T + F <= 224.
@@ -16,7 +16,7 @@ static GemmArgs lin(const float* A, int lda, const float* W, const float* bias, 
 
 int vae_encode(const EncoderW& w, const EncoderW* wsp, const float* features, const int32_t* lengths, const int32_t* counts,
                const float* eps, int B, int F, int T, int C, float* mu, float* sd, float* latent, float* ws,
-               size_t ws_floats, hipStream_t s) {
+               size_t ws_floats, hipStream_t s, const int32_t* slot, const float* values, int n_values) {
     const int S = 2 * T + F;
     if (F < 1 || S > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;
     EncWs a = enc_layout(ws, B, F, T, C);
@@ -52,7 +52,9 @@ int vae_encode(const EncoderW& w, const EncoderW* wsp, const float* features, co
     };
 
     // x = skel_embedding(features)  (K = nfeats is padded to a multiple of 32 columns)            ladiff_vae.py:182
-    LADIFF_TRY(launch_pad_cols(features, featp, B * F, C, Cp, s));
+    // DVAE (slot given): features + add_noise's field, in the same pass                                :136-150, :175-176
+    if (slot != nullptr) LADIFF_TRY(launch_dvae_pad_cols(features, slot, values, n_values, featp, B, F, C, Cp, s));
+    else LADIFF_TRY(launch_pad_cols(features, featp, B * F, C, Cp, s));
     LADIFF_TRY(launch_pad_cols(w.skel.w, wskel, D, C, Cp, s));
     LADIFF_TRY(launch_gemm(lin(featp, Cp, wskel, w.skel.b, emb, D, B * F, D, Cp), s));
     // xseq = cat(global_motion_token, x) + query_pos_encoder.pe;  key map from lengths / counts       :189-219

@@ -51,6 +51,9 @@ int launch_dec_qkv_attn(const float* xs, const float* w, const float* bias, cons
 int launch_scatter_feats(const float* tmp, int ldt, int C, int M, int F, const int32_t* row_len, const int32_t* row_map, float* feats,
                          hipStream_t s);
 int launch_pad_cols(const float* x, float* y, int R, int C, int Cp, hipStream_t s);
+// pad_cols of features [B,F,C] with the DVAE corruption added on the way: slot [F*C] (a column of values [B,n], or -1)
+int launch_dvae_pad_cols(const float* x, const int32_t* slot, const float* values, int n, float* y, int B, int F, int C, int Cp,
+                         hipStream_t s);
 int launch_encoder_assemble(const float* token, const float* emb, const float* pe, const int32_t* lengths,
                             const int32_t* counts, int B, int F, int T, float* x, float* xs, uint32_t* keybits, hipStream_t s);
 int launch_encoder_finalize(const float* out, const float* eps, const int32_t* counts, int B, int T, int S, float* mu, float* sd,
@@ -84,6 +87,11 @@ int launch_feats2joints(const float* feats, const float* mean, const float* stdv
 int launch_joint_ape_ave(const float* rst, const float* ref, const int32_t* lengths, int B, int F, int J, const int32_t* part_idx,
                          float factor, float* seq_rows, double* acc, hipStream_t s);
 int launch_joint_mr(const float* rst, const float* ref, int B, int F, int J, float* seq_rows, double* acc, hipStream_t s);
+
+// vae_losses.hip: the stage-"vae" losses of one batch (per-workgroup fp64 partial sums in fixed slots, then one workgroup adds them)
+int launch_vae_losses(const float* m_rst, const float* m_ref, size_t n_feat, const float* j_rst, const float* j_ref, size_t n_joint,
+                      const float* mu, const float* sd, size_t n_lat, double l_rec, double l_joint, double l_kl, double* part, int blocks,
+                      double* batch, double* acc, hipStream_t s);
 
 // attention.hip
 int launch_denoiser_self_attention(const float* qkv, const float* text_kv, const float* tables, int kv_off,

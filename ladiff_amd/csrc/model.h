@@ -57,7 +57,7 @@ int launch_dec_mlp(const float* xs, const float* x, const float* w1, const float
 
 int vae_encode(const EncoderW& w, const EncoderW* w_split, const float* features, const int32_t* lengths,
                const int32_t* counts, const float* eps, int B, int F, int T, int C, float* mu, float* sd, float* latent, float* ws,
-               size_t ws_floats, hipStream_t s);
+               size_t ws_floats, hipStream_t s, const int32_t* slot = nullptr, const float* values = nullptr, int n_values = 0);
 
 // systolic.hip: the guided denoiser loop as one persistent weight-stationary pipeline (both arithmetic modes); its host planner
 // (workspace carve, block packing, stage table, choose_plan) is systolic_plan.hip, declared in systolic_plan.h

@@ -390,6 +390,32 @@ int launch_pad_cols(const float* x, float* y, int R, int C, int Cp, hipStream_t 
     return 0;
 }
 
+// y[b F + f][c] = x[b][f][c] + (slot[f C + c] >= 0 ? values[b][slot[f C + c]] : 0) for c < C, zero for C <= c < Cp: pad_cols of the
+// features with LADiffVae.add_noise on the way (DVAE, ladiff_vae.py:136-150, :175-176: one standard normal per sample at each chosen
+// position of the flattened [F, C] frame block, the same positions for the whole batch).  A position without a slot keeps x's bits.
+__global__ __launch_bounds__(256) void dvae_pad_cols_kernel(const float* __restrict__ x, const int32_t* __restrict__ slot,
+                                                            const float* __restrict__ values, int n, float* __restrict__ y, int F, int C,
+                                                            int Cp, size_t total) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t r = i / Cp; const int c = (int)(i % Cp);
+    float v = 0.f;
+    if (c < C) {
+        v = x[r * C + c];
+        const int k = slot[(r % F) * C + c];
+        if (k >= 0 && k < n) v += values[(r / F) * n + k];         // never index by an unchecked device value
+    }
+    y[i] = v;
+}
+int launch_dvae_pad_cols(const float* x, const int32_t* slot, const float* values, int n, float* y, int B, int F, int C, int Cp,
+                         hipStream_t s) {
+    const size_t total = (size_t)B * F * Cp;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(dvae_pad_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, slot, values, n, y, F, C, Cp, total);
+    LADIFF_LAUNCH_CHECK();
+    return 0;
+}
+
 // xseq[b, s] = (s < 2T ? motion_token[s] : emb[b, s - 2T]) + pe[s]            ladiff_vae.py:189, :212, :219
 // keybits[b] = validity map of the S = 2T + F keys: mu tokens < count, logvar tokens < count, frames < len   :193-209
 __global__ __launch_bounds__(256) void encoder_assemble_kernel(const float* __restrict__ token, const float* __restrict__ emb,

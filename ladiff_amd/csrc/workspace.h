@@ -186,6 +186,26 @@ inline EncWs enc_layout(float* ws, int B, int F, int T, int C) {
 }
 inline size_t enc_ws_floats(int B, int F, int T, int C) { return enc_layout(nullptr, B, F, T, C).total; }
 
+// ------------------------------------------------------------------ stage-"vae" losses (vae_losses.hip)
+// [blocks][3] fp64 partial sums (recons_feature, recons_joints, kl_motion), one fixed slot per workgroup of the first launch.  The
+// workgroup count depends on the shapes alone (one per 256 16-byte chunks of the longest array, VAE_LOSS_MAX_BLOCKS at most), so the sums'
+// bits do not depend on the device.  The base must be 8-byte aligned.
+constexpr int VAE_LOSS_MAX_BLOCKS = 512;
+struct VaeLossWs { double* part; int blocks; size_t total; };
+inline VaeLossWs vae_losses_layout(float* ws, int B, int F, int C, int J, int T) {
+    VaeLossWs L;
+    Carver c(ws);
+    size_t n = (size_t)B * F * C;
+    for (size_t m : {(size_t)B * F * J * 3, (size_t)T * B * D})
+        if (m > n) n = m;
+    const size_t blocks = ((n + 3) / 4 + 255) / 256;
+    L.blocks = blocks < 1 ? 1 : (blocks > VAE_LOSS_MAX_BLOCKS ? VAE_LOSS_MAX_BLOCKS : (int)blocks);
+    L.part = reinterpret_cast<double*>(c.take((size_t)L.blocks * 3 * 2));
+    L.total = c.off;
+    return L;
+}
+inline size_t vae_losses_ws_floats(int B, int F, int C, int J, int T) { return vae_losses_layout(nullptr, B, F, C, J, T).total; }
+
 // ------------------------------------------------------------------ CLIP text tower
 constexpr int CLIP_W = LADIFF_TEXT_DIM;    // 768
 constexpr int CLIP_FF = 4 * CLIP_W;        // 3072

@@ -63,3 +63,16 @@ def evaluate(model, tm2t_batches, mm_batches, replication_times=1, metrics=None,
         mean, conf = get_metric_statistics(np.array(items), replication_times)
         stats[key] = (float(mean), float(conf))
     return stats, all_metrics
+
+
+def validate(model, batches, losses=None):
+    """The stage-1 validation quantities (`allsplit_step` of the reference in stage "vae", ladiff.py:1388-1412): every batch through
+    `model.train_vae_forward` into `losses.update(rs_set)`, then `losses.compute()` - {recons_feature, recons_joints, kl_motion, total,
+    ...: mean over the batches}.  `losses` = an `MLDLosses` to use (NOT reset here: a caller may accumulate over several calls);
+    default-constructed from `model.cfg` when None."""
+    if losses is None:
+        from .losses import MLDLosses
+        losses = MLDLosses(vae=getattr(model, "is_vae", True), cfg=getattr(model, "cfg", None), stage="vae")
+    for batch in batches:
+        losses.update(model.train_vae_forward(batch))
+    return losses.compute()

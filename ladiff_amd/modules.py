@@ -11,6 +11,7 @@ SKIP_CONNECT, MD_TRANS, mld PE, encoder_decoder VAE); other branches raise at co
 """
 import math
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -183,6 +184,9 @@ class LADiffVae(_HipModule):
         self.max_it = int(_get(ablation, "MAX_IT", 5))
         self.frame_per_latent = int(_get(ablation, "FRAME_PER_LATENT", 48))
         self.test_efficiency = bool(_get(ablation, "TEST_EFFICIENCY", False))
+        # denoising VAE: `encode` corrupts its input in every call, evaluation included (ladiff_vae.py:58-59, :175-176)
+        self.dvae = bool(_get(ablation, "DVAE", False))
+        self.percentage_noised = float(_get(ablation, "PERCENTAGE_NOISED", 0.0) or 0.0)
         self.length_aware = True        # decode only the valid frames of a mixed-length batch (same results, fewer rows)
         # Opt-in: decodes of fewer frame rows than this are replayed from a hipGraph over persistent buffers (0 = never, the default).
         # Measured on config c1 (8 x 60 frames, profiles/r3): 0.467 ms replayed against 0.458 ms launched directly - with the small-M
@@ -230,11 +234,39 @@ class LADiffVae(_HipModule):
             for lin in ("skel_embedding", "final_layer"):
                 _linear_default_(self.get_parameter(lin + ".weight"), self.get_parameter(lin + ".bias"))
 
-    def encode(self, features, lengths=None, eps=None):
+    def draw_corruption(self, B, F, device):
+        """The DVAE draw of one `encode` call on [B,F,nfeats] -> (positions LongTensor [n], values [B,n] on `device`): `add_noise`'s
+        `np.random.choice(F*C, int(F*C*p))` from the global numpy stream (the same call as the reference's, so `np.random.seed` selects
+        the same position set), its distinct values sorted, and one `torch.randn` per sample and distinct position."""
+        total = F * self.nfeats
+        positions = torch.from_numpy(np.unique(np.random.choice(total, int(total * self.percentage_noised))).astype(np.int64))
+        return positions, torch.randn(B, positions.numel(), dtype=torch.float32, device=device)
+
+    def _corruption_table(self, corrupt, B, F, dev):
+        """(slot int32 [F*C] on the device: column of `values` or -1, values [B,n] fp32 contiguous, n) from `corrupt`, checked on the host."""
+        positions, values = corrupt
+        positions = torch.as_tensor(positions).detach().to("cpu", torch.int64).reshape(-1)
+        n, total = positions.numel(), F * self.nfeats
+        if n and (int(positions.min()) < 0 or int(positions.max()) >= total or torch.unique(positions).numel() != n):
+            raise ValueError(f"corrupt positions must be distinct flat indices into [{F}, {self.nfeats}]")
+        if tuple(values.shape) != (B, n):
+            raise ValueError(f"corrupt values {tuple(values.shape)} for {B} samples x {n} positions")
+        slot = torch.full((total,), -1, dtype=torch.int32)
+        slot[positions] = torch.arange(n, dtype=torch.int32)
+        return slot.to(dev), values.detach().to(device=dev, dtype=torch.float32).contiguous(), n
+
+    def encode(self, features, lengths=None, eps=None, corrupt=None):
         """features [B,F,nfeats], lengths list[int] -> (latent [max_it,B,256], Normal(mu, std), max_iter_elements).
 
         `LADiffVae.encode` of the reference (ladiff_vae.py:162-286; LAD branch).  `eps` ([max_it,B,256], optional)
-        replaces the standard-normal draw of `dist.rsample()` so that results can be reproduced."""
+        replaces the standard-normal draw of `dist.rsample()` so that results can be reproduced.
+
+        `corrupt = (positions, values)` is the DVAE input corruption (`add_noise`, ladiff_vae.py:136-150): `positions` a LongTensor [n] of
+        DISTINCT flat indices into [F, nfeats], `values` [B, n]; the encoder reads `features[b].flatten()[positions[k]] + values[b, k]`.
+        With `DVAE` set in the ablation and `corrupt` None it is drawn here (`draw_corruption`, before `eps`), as the reference draws it in
+        every call; an explicit `corrupt` is honoured with or without `DVAE`.  The reference's `noise[:, idx] = randn` writes the duplicate
+        indices of its `np.random.choice` too, and which duplicate's value lands is neither the first nor the last nor stable between two
+        calls on the CPU; the values are i.i.d. standard normals, so one normal per distinct position has the same distribution."""
         L = _lib.lib()
         dev = features.device
         B, F, C = features.shape
@@ -249,6 +281,8 @@ class LADiffVae(_HipModule):
         counts = [int(math.ceil(l / self.frame_per_latent)) for l in lengths]
         lens_t = _lib.device_ints(lengths, dev)
         counts_t = _lib.device_ints(counts, dev)
+        if corrupt is None and self.dvae:
+            corrupt = self.draw_corruption(B, F, dev)                                     # add_noise runs before rsample
         if eps is None:
             eps = torch.randn(T, B, self.latent_dim, dtype=torch.float32, device=dev)     # Normal.rsample's draw
         eps = eps.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -257,9 +291,15 @@ class LADiffVae(_HipModule):
         mu, std, latent = (torch.empty(T, B, self.latent_dim, dtype=torch.float32, device=dev) for _ in range(3))
         wsb = L.ladiff_encoder_workspace_bytes(B, F, T, C)
         ws = _lib.workspace(wsb, dev)
-        _lib.check(L.ladiff_vae_encode(wt.array, wt.split_array() if _lib.is_split(self.precision) else None, _lib.ptr(x),
-                                       lens_t.data_ptr(), counts_t.data_ptr(), _lib.ptr(eps), B, F, T, C, _lib.ptr(mu),
-                                       _lib.ptr(std), _lib.ptr(latent), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+        wsplit = wt.split_array() if _lib.is_split(self.precision) else None
+        if corrupt is None:
+            _lib.check(L.ladiff_vae_encode(wt.array, wsplit, _lib.ptr(x), lens_t.data_ptr(), counts_t.data_ptr(), _lib.ptr(eps), B, F, T, C,
+                                           _lib.ptr(mu), _lib.ptr(std), _lib.ptr(latent), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+        else:
+            slot, values, n = self._corruption_table(corrupt, B, F, dev)
+            _lib.check(L.ladiff_vae_encode_dvae(wt.array, wsplit, _lib.ptr(x), lens_t.data_ptr(), counts_t.data_ptr(), _lib.ptr(eps), B, F,
+                                                T, C, _lib.ptr(mu), _lib.ptr(std), _lib.ptr(latent), _lib.ptr(ws), wsb, slot.data_ptr(),
+                                                _lib.ptr(values) if n else None, n, _lib.stream_ptr()))
         dist = torch.distributions.Normal(mu, std)
         return latent.to(features.dtype), dist, torch.tensor(counts, dtype=torch.long)
 

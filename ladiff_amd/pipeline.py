@@ -8,8 +8,10 @@ method names and call behaviour: `forward(batch)` (ladiff.py:250-308), `_diffusi
 tables, N x (denoiser, guidance, scheduler step) captured as one hipGraph step replayed N times, final masking -
 is ONE call into libladiff_hip.so; the decoder is a second one.  Nothing here falls back to PyTorch math.
 
-Out of scope (not built): training/eval steps, metrics, losses, the CLIP text encoder (pass any callable
-`texts -> [len(texts),1,768]`), `feats2joints` (pass the datamodule's).
+`cfg.TRAIN.STAGE` (or the `stage` keyword) selects what feeds the decoder: "diffusion" (the default) the loop above, "vae" the
+LA-VAE's own encoder on the batch's motion (stage 1: `t2m_eval`, `forward`, `mm_eval`, `train_vae_forward`).
+
+Out of scope (not built): training steps, the diffusion-stage losses, stage "vae_diffusion".
 """
 import importlib
 import math
@@ -70,7 +72,7 @@ class LADIFF(nn.Module):
     def __init__(self, cfg=None, datamodule=None, *, denoiser=None, vae=None, scheduler=None, text_encoder=None,
                  guidance_scale=None, num_inference_timesteps=None, eta=None, max_it=None, frame_per_latent=None,
                  test_efficiency=None, use_graph=True, precision=None, loop="pipeline", fallback=False,
-                 max_prompts_per_launch=320, mm_num_repeats=None, **kwargs):
+                 max_prompts_per_launch=320, mm_num_repeats=None, stage=None, **kwargs):
         super().__init__()
         self.cfg = cfg
         self.datamodule = datamodule
@@ -89,6 +91,15 @@ class LADIFF(nn.Module):
         self.test_efficiency = bool(pick(test_efficiency, abl, "TEST_EFFICIENCY", False))
         # motions generated per prompt in the multimodality pass (cfg.TEST.MM_NUM_REPEATS, ladiff.py:1122-1132; configs/base.yaml: 30)
         self.mm_num_repeats = int(pick(mm_num_repeats, _cfg_get(cfg, "TEST"), "MM_NUM_REPEATS", 30))
+        # cfg.TRAIN.STAGE (ladiff.py:72): "diffusion" = stage 2, text -> latents -> motion; "vae" = stage 1, the LA-VAE alone: t2m_eval /
+        # forward / mm_eval take their latents from vae.encode(motion) instead of the denoiser loop (ladiff.py:267-269, :1150-1198)
+        self.stage = str(pick(stage, _cfg_get(cfg, "TRAIN"), "STAGE", "diffusion"))
+        if self.stage == "vae_diffusion":
+            raise NotImplementedError('stage "vae_diffusion" (joint training of both stages) is not built')
+        if self.stage not in ("diffusion", "vae"):
+            raise ValueError(f"stage {self.stage!r} not supported")
+        self.condition = _cfg_get(model, "condition", "text")
+        self.is_vae = bool(_cfg_get(model, "vae", True))
         if _cfg_get(cfg, "ARDIFF", False) or _cfg_get(abl, "JOINT_DISTRO_FIX", False):
             raise NotImplementedError("ARDIFF / JOINT_DISTRO_FIX branches of _diffusion_reverse are not built")
         self.denoiser = denoiser if denoiser is not None else instantiate_from_config(_cfg_get(model, "denoiser"))
@@ -567,13 +578,18 @@ class LADIFF(nn.Module):
 
     def forward(self, batch, latentwise_gen=None, plot_att_map=None):
         texts, lengths = batch["text"], batch["length"]
-        if self.text_encoder is None or (self.feats2joints is None and self.feats2joints_device is None):
+        stage1 = self.stage == "vae"
+        if (self.text_encoder is None and not stage1) or (self.feats2joints is None and self.feats2joints_device is None):
             raise RuntimeError("LADIFF.forward needs a text_encoder callable and datamodule.feats2joints; "
                                "use .sample(text_emb, lengths) for embeddings -> features")
         self._check_loaded_weights()
         start = time.time()
-        text_emb = self.text_encoder(self._guided_texts(texts))
-        z = self._diffusion_reverse(text_emb, lengths)
+        if stage1:                                                  # ladiff.py:267-269
+            with torch.no_grad():
+                z, _, _ = self.vae.encode(batch["motion"].detach().to(self.device), lengths)
+        else:
+            text_emb = self.text_encoder(self._guided_texts(texts))
+            z = self._diffusion_reverse(text_emb, lengths)
         with torch.no_grad():
             if latentwise_gen:                                      # ladiff.py:274-283
                 lengths = list(lengths) * self.max_it
@@ -626,6 +642,68 @@ class LADIFF(nn.Module):
             rs_set["joints_ref"] = f2j(feats_ref)
         return rs_set
 
+    # ------------------------------------------------------------------ stage 1 (TRAIN.STAGE: vae): the LA-VAE alone
+    def _row_cuts(self, N):
+        """[lo, hi) row ranges of the encode / decode calls of a stage-1 multimodality pass: at most `max_prompts_per_launch` rows each."""
+        cap = N if self.max_prompts_per_launch is None else max(1, int(self.max_prompts_per_launch))
+        return [(lo, min(N, lo + cap)) for lo in range(0, N, cap)]
+
+    def _stage1_reconstruct(self, motions, lengths, cuts=None):
+        """The VAE branch of `t2m_eval` (ladiff.py:1150-1203): motions [N,F,C] -> (z [max_it,N,256], feats [N,max(lengths),C]) through
+        `vae.encode` -> `vae.decode`; `condition == "text_uncond"` replaces z with `torch.randn_like(z)` (:1196-1198).  `cuts` (row
+        ranges) runs the encode and the decode in several calls.  A result does not depend on the cuts: the rsample draws are ONE tensor
+        for the whole call and, under DVAE, so are the position set and its values - drawn here in the order one `vae.encode` call
+        draws them - each sliced per call."""
+        N, F = motions.shape[0], motions.shape[1]
+        cuts = cuts or [(0, N)]
+        with torch.no_grad():
+            if len(cuts) == 1:
+                z, _, _ = self.vae.encode(motions, lengths)
+            else:
+                corrupt = self.vae.draw_corruption(N, F, motions.device) if self.vae.dvae else None
+                eps = torch.randn(self.vae.max_it, N, 256, dtype=torch.float32, device=motions.device)
+                z = torch.cat([self.vae.encode(motions[lo:hi], lengths[lo:hi], eps=eps[:, lo:hi],
+                                               corrupt=None if corrupt is None else (corrupt[0], corrupt[1][lo:hi]))[0]
+                               for lo, hi in cuts], dim=1)
+            if self.condition == "text_uncond":
+                z = torch.randn_like(z)                              # uncond random sample
+            if len(cuts) == 1:
+                return z, self.vae.decode(z, lengths)
+            feats = None
+            for lo, hi in cuts:
+                part = self.vae.decode(z[:, lo:hi], lengths[lo:hi])
+                if feats is None:
+                    feats = torch.zeros(N, max(lengths), part.shape[-1], dtype=part.dtype, device=part.device)
+                feats[lo:hi, :part.shape[1]] = part
+        return z, feats
+
+    def train_vae_forward(self, batch):
+        """`LADIFF.train_vae_forward` (ladiff.py:815-871, `condition == "text"`) under `no_grad`: motion -> encode -> decode, the
+        reconstruction encoded again, both motions to joints.  Returns the reference's `rs_set`: m_ref, m_rst (cut to the shorter frame
+        count), lat_m, lat_rm [B,max_it,256], joints_ref, joints_rst, dist_m = Normal(mu, std) [max_it,B,256] and dist_ref (the standard
+        normal when `model.vae`, dist_m itself otherwise) - what `MLDLosses.update` takes."""
+        if self.condition != "text":
+            raise NotImplementedError(f"train_vae_forward with condition {self.condition!r} is not built")
+        if self.feats2joints is None and self.feats2joints_device is None:
+            raise RuntimeError("train_vae_forward needs datamodule.feats2joints")
+        self._check_loaded_weights()
+        lengths = [int(l) for l in batch["length"]]
+        feats_ref = batch["motion"].detach().to(self.device)
+        f2j = self.feats2joints_device or (lambda f: self.feats2joints(f.detach().cpu()))
+        with torch.no_grad():
+            motion_z, dist_m, _ = self.vae.encode(feats_ref, lengths)                    # :820-821
+            feats_rst = self.vae.decode(motion_z, lengths)
+            recons_z, _, _ = self.vae.encode(feats_rst, lengths)                         # :828
+        joints_rst, joints_ref = f2j(feats_rst), f2j(feats_ref)                          # :831-833
+        dist_ref = dist_m
+        if self.is_vae:                                                                  # :851-854
+            dist_ref = torch.distributions.Normal(torch.zeros_like(dist_m.loc), torch.ones_like(dist_m.scale))
+            dist_ref._ladiff_standard_normal = True
+        min_len = min(feats_ref.shape[1], feats_rst.shape[1])                            # :859
+        return {"m_ref": feats_ref[:, :min_len, :], "m_rst": feats_rst[:, :min_len, :], "lat_m": motion_z.permute(1, 0, 2),
+                "lat_rm": recons_z.permute(1, 0, 2), "joints_ref": joints_ref, "joints_rst": joints_rst, "dist_m": dist_m,
+                "dist_ref": dist_ref}
+
     def set_t2m_evaluators(self, text_encoder, movement_encoder, motion_encoder, unit_len=4):
         """The three frozen evaluator networks of `_get_t2m_evaluator` (ladiff.py:179-223); `unit_len` =
         cfg.DATASET.HUMANML3D.UNIT_LEN (ladiff.py:1259-1261)."""
@@ -636,11 +714,13 @@ class LADIFF(nn.Module):
         self.t2m_unit_len = int(unit_len)
 
     def t2m_eval(self, batch):
-        """Text -> motion -> evaluator embeddings for the TM2T metrics (`ladiff.py:1111-1282`, diffusion stage): returns the
-        reference's `rs_set` (m_ref, m_rst, lat_t, lat_m, lat_rm, joints_ref, joints_rst), sequences sorted by length."""
+        """Text -> motion -> evaluator embeddings for the TM2T metrics (`ladiff.py:1111-1282`): returns the reference's `rs_set`
+        (m_ref, m_rst, lat_t, lat_m, lat_rm, joints_ref, joints_rst), sequences sorted by length.  In stage "vae" the motion comes from
+        `vae.encode(batch["motion"])` -> `vae.decode` instead of text and the denoiser loop: no text encoder call, no loop launch."""
         if getattr(self, "t2m_motionencoder", None) is None:
             raise RuntimeError("call set_t2m_evaluators(text_encoder, movement_encoder, motion_encoder) first")
-        if self.text_encoder is None or not hasattr(self.datamodule, "renorm4t2m"):
+        stage1 = self.stage == "vae"
+        if (self.text_encoder is None and not stage1) or not hasattr(self.datamodule, "renorm4t2m"):
             raise RuntimeError("t2m_eval needs a text_encoder and datamodule.renorm4t2m / feats2joints")
         self._check_loaded_weights()
         if getattr(self.datamodule, "is_mm", False):                                  # ladiff.py:1122-1132
@@ -649,10 +729,13 @@ class LADIFF(nn.Module):
         dev = self.device
         motions = batch["motion"].detach().clone().to(dev)
         start = time.time()
-        text_emb = self.text_encoder(self._guided_texts(texts))                       # ladiff.py:1135-1144
-        z = self._diffusion_reverse(text_emb, lengths)
-        with torch.no_grad():
-            feats_rst = self.vae.decode(z, lengths)        # [B, max(lengths), nfeats], frames >= length are zero (:1196-1207)
+        if stage1:                                         # the motion itself through the LA-VAE, un-renormalised (ladiff.py:1150-1198)
+            _, feats_rst = self._stage1_reconstruct(motions, lengths)
+        else:
+            text_emb = self.text_encoder(self._guided_texts(texts))                   # ladiff.py:1135-1144
+            z = self._diffusion_reverse(text_emb, lengths)
+            with torch.no_grad():
+                feats_rst = self.vae.decode(z, lengths)    # [B, max(lengths), nfeats], frames >= length are zero (:1196-1207)
         torch.cuda.synchronize()
         self.check()
         self.times.append(time.time() - start)
@@ -702,11 +785,14 @@ class LADIFF(nn.Module):
         src_t = torch.as_tensor(src, device=dev)
         motions0 = batch["motion"].detach().clone().to(dev)
         start = time.time()
-        encoded, row_of_text = self._encode_distinct(texts0)
-        text_emb = self._expanded_text(encoded, [row_of_text[i % B] for i in range(N)])
-        z = self._diffusion_reverse(text_emb, lengths)
-        with torch.no_grad():
-            feats_rst = self.vae.decode(z, lengths)
+        if self.stage == "vae":                                # every motion R times through encode -> decode, each with its own draws
+            _, feats_rst = self._stage1_reconstruct(motions0[src_t], lengths, self._row_cuts(N))
+        else:
+            encoded, row_of_text = self._encode_distinct(texts0)
+            text_emb = self._expanded_text(encoded, [row_of_text[i % B] for i in range(N)])
+            z = self._diffusion_reverse(text_emb, lengths)
+            with torch.no_grad():
+                feats_rst = self.vae.decode(z, lengths)
         torch.cuda.synchronize()
         self.check()
         self.times.append(time.time() - start)
@@ -762,11 +848,18 @@ class LADIFF(nn.Module):
         sample index (`noise_first_prompt` + prompt * R + repeat) with one `noise_seed` for the call - up to the rounding of another
         block packing inside the loop.  The evaluators see every prompt's R motions as a batch of that prompt's own
         length, as the reference's one-prompt MM batches do (the movement encoder's last output looks one frame past the length, so its
-        value depends on the padding); there is no longest-first sort to undo."""
+        value depends on the padding); there is no longest-first sort to undo.
+
+        In stage "vae" (`batch` also carries `motion` [B,F,nfeats]) every motion goes R times through `vae.encode` -> `vae.decode` -
+        R draws of the posterior (and of the DVAE corruption) per motion - in calls of at most `max_prompts_per_launch` rows with the
+        draws made once for the whole call (`_stage1_reconstruct`); the output has the same structure."""
         if getattr(self, "t2m_motionencoder", None) is None:
             raise RuntimeError("call set_t2m_evaluators(text_encoder, movement_encoder, motion_encoder) first")
-        if self.text_encoder is None or not hasattr(self.datamodule, "renorm4t2m"):
+        stage1 = self.stage == "vae"
+        if (self.text_encoder is None and not stage1) or not hasattr(self.datamodule, "renorm4t2m"):
             raise RuntimeError("mm_eval needs a text_encoder and datamodule.renorm4t2m / feats2joints")
+        if stage1 and (init_noise is not None or noise_seed is not None):
+            raise ValueError('init_noise / noise_seed belong to the denoiser loop; stage "vae" has none')
         if self.test_efficiency:
             raise NotImplementedError("mm_eval with TEST_EFFICIENCY (a latent count per launch) is not built")
         self._check_loaded_weights()
@@ -777,6 +870,8 @@ class LADIFF(nn.Module):
             raise ValueError("mm_eval needs B >= 1 prompts with one length each and repeats >= 1")
         N, T, dev = B * R, self.max_it, self.device
         lengths = [l for l in lengths0 for _ in range(R)]
+        if stage1:
+            return self._mm_finish(*self._mm_stage1(batch, lengths, B, R), lengths0, lengths, R)
         if init_noise is None:
             init_noise = torch.randn(N, T, 256, device=dev, dtype=torch.float32)
         elif tuple(init_noise.shape) != (N, T, 256):
@@ -801,6 +896,22 @@ class LADIFF(nn.Module):
                 feats[s0:s1, :part.shape[1]] = part
         finally:
             self.noise_first_prompt = base
+        return self._mm_finish(feats, start, lengths0, lengths, R)
+
+    def _mm_stage1(self, batch, lengths, B, R):
+        """`mm_eval` in stage "vae": motion b of `batch["motion"]` R times through encode -> decode (sample b * R + r is repeat r of
+        motion b), in calls of at most `max_prompts_per_launch` ROWS (`last_mm_launches` keeps the row ranges) -> (feats, start time)."""
+        motions0 = batch["motion"].detach().to(self.device)
+        if motions0.shape[0] != B:
+            raise ValueError(f"{motions0.shape[0]} motions for {B} prompts")
+        start = time.time()
+        self.last_mm_launches = self._row_cuts(B * R)
+        _, feats = self._stage1_reconstruct(motions0.repeat_interleave(R, dim=0), lengths, self.last_mm_launches)
+        return feats, start
+
+    def _mm_finish(self, feats, start, lengths0, lengths, R):
+        """The second half of `mm_eval`, shared by both stages: joints, renormalisation, evaluator embeddings per prompt length."""
+        B, dev = len(lengths0), self.device
         torch.cuda.synchronize()
         self.check()
         self.times.append(time.time() - start)
