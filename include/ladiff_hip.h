@@ -437,6 +437,44 @@ LADIFF_API int ladiff_vae_losses(const float* m_rst, const float* m_ref, const f
                       double lambda_joint, double lambda_kl, double* batch, double* acc, void* ws, size_t ws_bytes,
                       ladiff_stream_t stream);
 
+/* ------------------------------------------------------------------ stage "diffusion" outside the sampling loop (csrc/diffusion_stage.hip)
+ * LADIFF._diffusion_process (ladiff.py:745-813) in the shipped branch (IDEA 'ard', ARDIFF False, LAD True, PREDICT_EPSILON True):
+ * q-sample, the denoiser with ONE TIMESTEP PER SAMPLE, and MLDLosses' inst_loss (losses/mld.py:69, :112).
+ *
+ * ladiff_denoiser_forward_timesteps: eps[B2,T,256] = denoiser(sample[B2,T,256], timesteps[B2] (int64, device), text_emb[B2,768]) for one
+ * text token (n_text != 1: LADIFF_ERR_UNSUPPORTED), counts[B2] latent counts or NULL, both arithmetic modes (w_split NULL = fp32).  Unlike
+ * ladiff_denoiser_forward it takes no tables, step counter or text cache: those are per CALL there and per SAMPLE here, so the entry
+ * builds them in its workspace - the sinusoid and the time tables with row b = sample b's timestep, the step-invariant text cache, and a
+ * "diagonal" c table [9][B2][valid | pad][256] (the padded rows' vector depends on the sample's timestep too) - and the three row kernels
+ * that read the step counter in the loop read table row b instead.  The launch count does not depend on B2 and the workspace is O(B2 T).
+ * f16x3 mode runs the unfused sequence (split-operand GEMMs + row kernels that write the S-format twin).  With equal timesteps the result
+ * equals ladiff_denoiser_forward's within the fp32 gate (5e-6 measured in both modes; not bit for bit: the time-table GEMMs run on B2
+ * rows here and on one row there, and the f16x3 kernels differ).  All pointers 16-byte aligned
+ * (timesteps 8, counts 4): LADIFF_ERR_SHAPE otherwise and for T outside 1 .. LADIFF_MAX_LATENTS.  The query is non-decreasing.
+ *
+ * ladiff_q_sample, one launch: noisy[b,t,:] = sqrt(acp[ts[b]]) z[t,b,:] + sqrt(1 - acp[ts[b]]) noise[b,t,:] (scheduler.add_noise; z is
+ * sequence-first [T,B,256] as vae.encode returns it: the read folds the permute of ladiff.py:939 in), rows t >= counts[b] of noisy zero
+ * (ladiff.py:779-782; counts NULL: none); rows of noise are never zeroed (the loss runs over all of them).  alphas_cumprod[n_train]
+ * fp32 on the device; 0 <= ts[b] < n_train is the caller's contract (a value outside is clamped so that the read stays inside the table,
+ * never reported).  Coefficients and sum in fp64, rounded once.  draw == 0: noise is the caller's input.
+ * draw != 0: noise is an OUTPUT, drawn in the kernel from the counter-based generator at schedule position 0 for global prompts
+ * first_prompt + b - the values of ladiff_noise_fill(seed, first_prompt, 0, 1, B, T).
+ *
+ * ladiff_diffusion_losses: inst_loss = mean (noise_pred - noise)^2 over n elements (all B T 256, padded rows included), total =
+ * lambda_inst inst_loss (the reference: 1).  batch[2] (device fp64) receives {inst_loss, total}; acc[2] gains them without a host
+ * synchronisation.  fp64 throughout, two launches over fixed partial-sum slots, no floating-point atomics: same inputs, same bits.
+ * LADIFF_ERR_SHAPE for n < 1 or a misaligned pointer (inputs 4 bytes; batch, acc, ws 8). */
+LADIFF_API size_t ladiff_denoiser_forward_timesteps_workspace_bytes(int B2, int T);
+LADIFF_API int ladiff_denoiser_forward_timesteps(const float* const* w, const float* const* w_split /*or NULL*/, const float* text_emb,
+                      int n_text, const int64_t* timesteps /*[B2]*/, const float* sample, int B2, int T, const int32_t* counts /*or NULL*/,
+                      float* eps, void* ws, size_t ws_bytes, ladiff_stream_t stream);
+LADIFF_API int ladiff_q_sample(const float* z, const int64_t* timesteps, const float* alphas_cumprod, int n_train,
+                      const int32_t* counts /*or NULL*/, int draw, uint64_t seed, uint32_t first_prompt, float* noise, float* noisy,
+                      int B, int T, ladiff_stream_t stream);
+LADIFF_API size_t ladiff_diffusion_losses_workspace_bytes(int64_t n);
+LADIFF_API int ladiff_diffusion_losses(const float* noise_pred, const float* noise, int64_t n, double lambda_inst, double* batch,
+                      double* acc, void* ws, size_t ws_bytes, ladiff_stream_t stream);
+
 /* ------------------------------------------------------------------ CLIP text encoder (the caller side)
  * MldTextEncoder.forward, mld_clip.py:51-86, "clip" branch (call sites ladiff.py:265, :1048, :1144):
  * text_model.get_text_features(input_ids) of transformers' CLIPModel -> out[B,768] (the reference then unsqueezes to

@@ -12,7 +12,7 @@ from .evaluators import (MovementConvEncoder, MotionEncoderBiGRUCo, TextEncoderB
                          TM2TMetrics, MMMetrics)
 from .evaluation import evaluate, get_metric_statistics, validate   # noqa: F401
 from .joint_metrics import ComputeMetrics, MRMetrics, TemosMetric   # noqa: F401
-from .losses import MLDLosses   # noqa: F401
+from .losses import DiffusionLosses, MLDLosses   # noqa: F401
 
 __all__ = ["LADiffDenoiser", "LADiffVae", "LADIFF", "DDIMScheduler", "DDPMScheduler", "instantiate_from_config", "Feats2Joints", "MldTextEncoder", "MovementConvEncoder", "MotionEncoderBiGRUCo", "TextEncoderBiGRUCo",
-           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics", "validate", "MLDLosses"]
+           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics", "validate", "MLDLosses", "DiffusionLosses"]

@@ -117,6 +117,13 @@ _SIGNATURES = {
     "ladiff_vae_losses_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "ladiff_vae_losses": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ladiff_denoiser_forward_timesteps_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ladiff_denoiser_forward_timesteps": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                                  c_void_p, c_size_t, c_void_p]),
+    "ladiff_q_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_uint64, ctypes.c_uint32, c_void_p, c_void_p, c_int,
+                                c_int, c_void_p]),
+    "ladiff_diffusion_losses_workspace_bytes": (c_size_t, [ctypes.c_int64]),
+    "ladiff_diffusion_losses": (c_int, [c_void_p, c_void_p, ctypes.c_int64, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ladiff_clip_num_params": (c_int, []),
     "ladiff_clip_param_name": (c_char_p, [c_int]),
     "ladiff_clip_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -510,6 +510,53 @@ int ladiff_vae_losses(const float* m_rst, const float* m_ref, const float* joint
                              lambda_rec, lambda_joint, lambda_kl, a.part, a.blocks, batch, acc, S(stream));
 }
 
+// ------------------------------------------------------------------ stage "diffusion" (csrc/diffusion_stage.hip)
+size_t ladiff_denoiser_forward_timesteps_workspace_bytes(int B2, int T) { return den_per_sample_ws_floats(B2, T) * sizeof(float); }
+
+int ladiff_denoiser_forward_timesteps(const float* const* w, const float* const* w_split, const float* text_emb, int n_text,
+                                      const int64_t* timesteps, const float* sample, int B2, int T, const int32_t* counts, float* eps,
+                                      void* ws, size_t ws_bytes, ladiff_stream_t stream) {
+    DenoiserW W, WS;
+    LADIFF_CHECK_ARG(load_weights(W, w) && text_emb && timesteps && sample && eps && ws);
+    if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
+    if (n_text != 1) return LADIFF_ERR_UNSUPPORTED;
+    if (B2 < 1 || T < 1 || T > LADIFF_MAX_LATENTS) return LADIFF_ERR_SHAPE;
+    for (const void* p : {(const void*)text_emb, (const void*)sample, (const void*)eps, (const void*)ws})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return LADIFF_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(timesteps) & 7) || (reinterpret_cast<uintptr_t>(counts) & 3)) return LADIFF_ERR_SHAPE;
+    if (ws_bytes < ladiff_denoiser_forward_timesteps_workspace_bytes(B2, T)) return LADIFF_ERR_WORKSPACE;
+    return denoiser_forward_timesteps(W, w_split ? &WS : nullptr, text_emb, timesteps, sample, B2, T, counts, eps, (float*)ws,
+                                      ws_bytes / sizeof(float), S(stream));
+}
+
+int ladiff_q_sample(const float* z, const int64_t* timesteps, const float* alphas_cumprod, int n_train, const int32_t* counts, int draw,
+                    uint64_t seed, uint32_t first_prompt, float* noise, float* noisy, int B, int T, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(z && timesteps && alphas_cumprod && noise && noisy && n_train > 0);
+    if (B < 1 || T < 1 || T > LADIFF_MAX_LATENTS) return LADIFF_ERR_SHAPE;
+    for (const void* p : {(const void*)z, (const void*)noise, (const void*)noisy})
+        if (reinterpret_cast<uintptr_t>(p) & 15) return LADIFF_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(timesteps) & 7) || (reinterpret_cast<uintptr_t>(alphas_cumprod) & 3) ||
+        (reinterpret_cast<uintptr_t>(counts) & 3))
+        return LADIFF_ERR_SHAPE;
+    return launch_q_sample(z, timesteps, alphas_cumprod, n_train, counts,
+                           NoiseGen{(unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), first_prompt, draw ? 1 : 0}, noise, noisy, B, T,
+                           S(stream));
+}
+
+size_t ladiff_diffusion_losses_workspace_bytes(int64_t n) { return n < 1 ? 0 : diffusion_losses_layout(nullptr, (size_t)n).total * sizeof(float); }
+
+int ladiff_diffusion_losses(const float* noise_pred, const float* noise, int64_t n, double lambda_inst, double* batch, double* acc, void* ws,
+                            size_t ws_bytes, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(noise_pred && noise && batch && acc && ws);
+    if (n < 1) return LADIFF_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(noise_pred) & 3) || (reinterpret_cast<uintptr_t>(noise) & 3)) return LADIFF_ERR_SHAPE;
+    for (const void* p : {(const void*)batch, (const void*)acc, (const void*)ws})
+        if (reinterpret_cast<uintptr_t>(p) & 7) return LADIFF_ERR_SHAPE;
+    const DiffLossWs a = diffusion_losses_layout((float*)ws, (size_t)n);
+    if (ws_bytes / sizeof(float) < a.total) return LADIFF_ERR_WORKSPACE;
+    return launch_diffusion_losses(noise_pred, noise, (size_t)n, lambda_inst, a.part, a.blocks, batch, acc, S(stream));
+}
+
 // ------------------------------------------------------------------ CLIP text encoder
 int ladiff_clip_num_params(void) { return CLIP_NPARAMS; }
 const char* ladiff_clip_param_name(int i) { return name_at(clip_param_names(), i); }

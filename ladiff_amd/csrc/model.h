@@ -26,6 +26,15 @@ int denoiser_ctab(const DenoiserW& w, const float* tables_lo, int n, float* cach
 int linear_cross_attention(const DenoiserW& w, int layer, const float* x, const float* xf, const float* emb, const int32_t* counts,
                            int B, int T, int N, float* out, float* ws, size_t ws_floats, hipStream_t s);
 
+// diffusion_stage.hip: the forward with one timestep per sample (stage "diffusion" outside the sampling loop; one text token) in `ws`
+// (den_per_sample_layout), q-sample, and the noise-prediction loss
+int denoiser_forward_timesteps(const DenoiserW& w, const DenoiserW* w_split, const float* text, const int64_t* timesteps, const float* sample,
+                               int B2, int T, const int32_t* counts, float* eps, float* ws, size_t ws_floats, hipStream_t s);
+int launch_q_sample(const float* z, const int64_t* ts, const float* acp, int n_train, const int32_t* counts, const NoiseGen& gen, float* noise,
+                    float* noisy, int B, int T, hipStream_t s);
+int launch_diffusion_losses(const float* pred, const float* noise, size_t n, double lambda_inst, double* part, int blocks, double* batch,
+                            double* acc, hipStream_t s);
+
 // reverse.hip: the whole reverse loop of ladiff_diffusion_reverse (arguments checked by the caller); sp may be null (plain launches)
 struct Sampler;      // sampler.h
 int diffusion_reverse(Sampler* sp, const DenoiserW& w, const DenoiserW* w_split, const ReverseArgs& a);

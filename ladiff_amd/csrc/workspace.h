@@ -206,6 +206,51 @@ inline VaeLossWs vae_losses_layout(float* ws, int B, int F, int C, int J, int T)
 }
 inline size_t vae_losses_ws_floats(int B, int F, int C, int J, int T) { return vae_losses_layout(nullptr, B, F, C, J, T).total; }
 
+// ------------------------------------------------------------------ stage "diffusion": forward with one timestep per sample
+// (diffusion_stage.hip).  Everything is per SAMPLE, where the sampling loop's tables are per STEP:
+//   sinus   [B2][768]          sinusoid of sample b's timestep
+//   tables  [B2][9][1536]      the time tables with row = sample (den_tables_floats(B2): the step axis of the loop's layout)
+//   cache   the step-invariant text cache (den_text_cache_layout with n = 0: no c table inside)
+//   dctab   [9][B2][2][256]    "diagonal" c table: c[layer][b][0] for sample b's valid rows and c[layer][b][1] for its padded rows,
+//                              both under sample b's OWN timestep - 2 B2 rows per layer where the loop's [n][B2 + 1] would be B2 (B2 + 1)
+//   u       [9][B2][2][256]    inputs of the out-projection that yields dctab (S-format in f16x3 mode)
+//   tws     scratch of denoiser_time_tables for B2 rows | xws  scratch of denoiser_text_static | fwd  the layers' scratch
+// O(B2 T) in all; the regions do not share space (a few hundred KiB per sample at most).
+struct DenPerSampleWs { float *sinus, *tables, *cache, *dctab, *u, *tws, *xws, *fwd; size_t tws_floats, xws_floats, fwd_floats, total; };
+inline DenPerSampleWs den_per_sample_layout(float* ws, int B2, int T) {
+    DenPerSampleWs L;
+    Carver c(ws, 64);
+    L.sinus = c.take((size_t)B2 * TEXT_DIM);
+    L.tables = c.take(den_tables_floats(B2));
+    L.cache = c.take(den_text_cache_floats(B2, 0, 1));
+    L.dctab = c.take((size_t)NL * B2 * 2 * D);
+    L.u = c.take((size_t)NL * B2 * 2 * D);
+    L.tws_floats = den_time_layout(nullptr, B2).total;
+    L.tws = c.take(L.tws_floats);
+    L.xws_floats = den_text_ws_floats(B2, 0, 1);
+    L.xws = c.take(L.xws_floats);
+    L.fwd_floats = den_forward_ws_floats(B2, T);
+    L.fwd = c.take(L.fwd_floats);
+    L.total = c.off;
+    return L;
+}
+inline size_t den_per_sample_ws_floats(int B2, int T) { return den_per_sample_layout(nullptr, B2, T).total; }
+
+// ------------------------------------------------------------------ stage-"diffusion" loss (diffusion_stage.hip)
+// [blocks] fp64 partial sums of (noise_pred - noise)^2, one fixed slot per workgroup of the first launch; the workgroup count depends on
+// n alone (one per 256 16-byte chunks, DIFF_LOSS_MAX_BLOCKS at most).  The base must be 8-byte aligned.
+constexpr int DIFF_LOSS_MAX_BLOCKS = 512;
+struct DiffLossWs { double* part; int blocks; size_t total; };
+inline DiffLossWs diffusion_losses_layout(float* ws, size_t n) {
+    DiffLossWs L;
+    Carver c(ws);
+    const size_t blocks = ((n + 3) / 4 + 255) / 256;
+    L.blocks = blocks < 1 ? 1 : (blocks > DIFF_LOSS_MAX_BLOCKS ? DIFF_LOSS_MAX_BLOCKS : (int)blocks);
+    L.part = reinterpret_cast<double*>(c.take((size_t)L.blocks * 2));
+    L.total = c.off;
+    return L;
+}
+
 // ------------------------------------------------------------------ CLIP text tower
 constexpr int CLIP_W = LADIFF_TEXT_DIM;    // 768
 constexpr int CLIP_FF = 4 * CLIP_W;        // 3072

@@ -65,14 +65,23 @@ def evaluate(model, tm2t_batches, mm_batches, replication_times=1, metrics=None,
     return stats, all_metrics
 
 
-def validate(model, batches, losses=None):
-    """The stage-1 validation quantities (`allsplit_step` of the reference in stage "vae", ladiff.py:1388-1412): every batch through
-    `model.train_vae_forward` into `losses.update(rs_set)`, then `losses.compute()` - {recons_feature, recons_joints, kl_motion, total,
-    ...: mean over the batches}.  `losses` = an `MLDLosses` to use (NOT reset here: a caller may accumulate over several calls);
-    default-constructed from `model.cfg` when None."""
+def validate(model, batches, losses=None, *, stage="vae"):
+    """The validation quantities of `allsplit_step` in the reference (ladiff.py:1388-1412): every batch through the stage's training
+    forward into `losses.update(rs_set)`, then `losses.compute()` - the mean over the batches of each loss.
+    stage "vae" (the default): `model.train_vae_forward` into an `MLDLosses` - {recons_feature, recons_joints, kl_motion, total, ...}.
+    stage "diffusion", or a `DiffusionLosses` passed in: `model.train_diffusion_forward` (random timesteps, noise and text drop, as the
+    reference's validation step draws them) into a `DiffusionLosses` - {inst_loss, x_loss, total}.
+    `losses` = the object to use (NOT reset here: a caller may accumulate over several calls); default-constructed from `model.cfg`."""
+    from .losses import DiffusionLosses, MLDLosses
+    if isinstance(losses, DiffusionLosses):
+        stage = "diffusion"
+    if stage not in ("vae", "diffusion"):
+        raise ValueError(f"stage {stage!r} not supported")
     if losses is None:
-        from .losses import MLDLosses
-        losses = MLDLosses(vae=getattr(model, "is_vae", True), cfg=getattr(model, "cfg", None), stage="vae")
+        cls = DiffusionLosses if stage == "diffusion" else MLDLosses
+        kw = {} if stage == "diffusion" else {"stage": "vae"}
+        losses = cls(vae=getattr(model, "is_vae", True), cfg=getattr(model, "cfg", None), **kw)
+    forward = model.train_diffusion_forward if stage == "diffusion" else model.train_vae_forward
     for batch in batches:
-        losses.update(model.train_vae_forward(batch))
+        losses.update(forward(batch))
     return losses.compute()

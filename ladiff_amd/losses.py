@@ -2,8 +2,10 @@
 `recons_joints`, `kl_motion` and `total`, fed with the `rs_set` of `LADIFF.train_vae_forward` (ladiff.py:815-871).  `update()` queues two
 launches (`ladiff_vae_losses`: per-workgroup fp64 partial sums, then one workgroup adds them, divides and adds the four values to an fp64
 accumulator on the device - the reference's `+=` per update) and returns the batch's `total` as a 0-dim device tensor without
-synchronising; `compute()` copies the accumulator once and divides by the update count.  There is no CPU implementation, and the
-diffusion-stage losses (training quantities of stage 2) are not built.
+synchronising; `compute()` copies the accumulator once and divides by the update count.  There is no CPU implementation.
+
+Stage "diffusion" is `DiffusionLosses` below: `inst_loss` (the noise-prediction MSE of `LADIFF.train_diffusion_forward`'s `n_set`) and
+`total`, through `ladiff_diffusion_losses`, with the same interface.
 """
 import numpy as np
 import torch
@@ -27,7 +29,8 @@ class MLDLosses:
         if stage not in ("vae", "diffusion", "vae_diffusion"):
             raise ValueError(f"Stage {stage} not supported")
         if stage != "vae":
-            raise NotImplementedError(f'MLDLosses(stage={stage!r}) is not built: only the stage-"vae" losses run on the GPU')
+            raise NotImplementedError(f'MLDLosses(stage={stage!r}) is not built: this class holds the stage-"vae" losses; the stage-'
+                                      '"diffusion" losses are DiffusionLosses')
         if _cfg_get(_cfg_get(_cfg_get(cfg, "TRAIN"), "ABLATION"), "JOINT_DISTRO_FIX", False):
             raise NotImplementedError("MLDLosses with JOINT_DISTRO_FIX (KLLossMulti) is not built")
         self.vae, self.mode, self.cfg, self.stage = vae, mode, cfg, stage
@@ -121,3 +124,82 @@ class MLDLosses:
             return f"{loss}/{split}"
         loss_type, name = loss.split("_")
         return f"{loss_type}/{name}/{split}"
+
+
+# the reference's state names in stage "diffusion" with LAMBDA_PRIOR == 0, in its order (mld.py:30-36, :53)
+DIFFUSION_STAGE_LOSSES = ("inst_loss", "x_loss", "total")
+_DIFF_COMPUTED = ("inst_loss", "total")                                     # layout of the device accumulator
+
+
+class DiffusionLosses:
+    """`MLDLosses(vae, mode, cfg)` of the reference in stage "diffusion" (mld.py:30-36, :108-120): `inst_loss` = `nn.MSELoss` of
+    `noise_pred` against `noise` over every element, padded latent rows included, and `total` = 1 x `inst_loss` (mld.py:67-69).  `x_loss`
+    belongs to `PREDICT_EPSILON: False` and stays 0.0; that branch and the prior loss (`LOSS.LAMBDA_PRIOR != 0`) are not built.  Same
+    interface and the same device-side accumulation as `MLDLosses`."""
+
+    def __init__(self, vae=True, mode="xyz", cfg=None, *, predict_epsilon=None, lambda_prior=None):
+        abl = _cfg_get(_cfg_get(cfg, "TRAIN"), "ABLATION")
+        if predict_epsilon is None:
+            predict_epsilon = _cfg_get(abl, "PREDICT_EPSILON", True)
+        if lambda_prior is None:
+            lambda_prior = _cfg_get(_cfg_get(cfg, "LOSS"), "LAMBDA_PRIOR", 0.0)
+        if not predict_epsilon:
+            raise NotImplementedError("DiffusionLosses with PREDICT_EPSILON: False (x_loss) is not built")
+        if float(lambda_prior) != 0.0:
+            raise NotImplementedError("DiffusionLosses with LAMBDA_PRIOR != 0 (prior_loss) is not built")
+        self.vae, self.mode, self.cfg, self.stage = vae, mode, cfg, "diffusion"
+        self.losses = list(DIFFUSION_STAGE_LOSSES)
+        self._params = {"inst_loss": 1.0, "x_loss": 1.0}                    # mld.py:67-72
+        self.reset()
+
+    def reset(self):
+        self.count = 0
+        self._host = np.zeros(len(_DIFF_COMPUTED), dtype=np.float64)
+        self._acc = None                                                    # fp64 [2] on the device the updates run on
+        self.last_batch = None                                              # fp64 [2] device tensor of the latest update
+
+    def update(self, rs_set):
+        """One batch: `noise_pred` and `noise`, two tensors of one shape (`_diffusion_process`'s `n_set`).  Returns the batch's `total`."""
+        pred, noise = rs_set["noise_pred"], rs_set["noise"]
+        if not torch.is_tensor(pred) or not torch.is_tensor(noise) or pred.shape != noise.shape or pred.numel() == 0:
+            raise _lib.LadiffHipError("noise_pred / noise must be two non-empty tensors of one shape")
+        device = next((t.device for t in (pred, noise) if t.is_cuda), None)
+        if device is None:
+            if not torch.cuda.is_available():
+                raise _lib.LadiffHipError("the losses run on the GPU only; got CPU tensors and there is no GPU (no CPU fallback exists)")
+            device = torch.device("cuda", torch.cuda.current_device())
+        L = _lib.lib()
+        with torch.cuda.device(device):
+            a, b = (t.detach().to(device=device, dtype=torch.float32).contiguous() for t in (pred, noise))
+            if self._acc is not None and self._acc.device != device:
+                self._host += self._acc.cpu().numpy()
+                self._acc = None
+            if self._acc is None:
+                self._acc = torch.zeros(len(_DIFF_COMPUTED), dtype=torch.float64, device=device)
+            batch = torch.empty(len(_DIFF_COMPUTED), dtype=torch.float64, device=device)
+            wsb = L.ladiff_diffusion_losses_workspace_bytes(a.numel())
+            ws = torch.empty((wsb + 7) // 8, dtype=torch.float64, device=device)
+            _lib.check(L.ladiff_diffusion_losses(a.data_ptr(), b.data_ptr(), a.numel(), self._params["inst_loss"], batch.data_ptr(),
+                                                 self._acc.data_ptr(), ws.data_ptr(), wsb, torch.cuda.current_stream(device).cuda_stream))
+        self.last_batch = batch
+        self.count += 1
+        return batch[1]
+
+    def sums(self):
+        """{"count", "sums"}: the update count and the fp64 sums [inst_loss, total] as a numpy array (waits for the queued updates)."""
+        total = self._host.copy()
+        if self._acc is not None:
+            total += self._acc.cpu().numpy()
+        return {"count": self.count, "sums": total}
+
+    add_sums = MLDLosses.add_sums
+    loss2logname = MLDLosses.loss2logname
+
+    def compute(self, split=None):
+        """{loss: sum / count} over the reference's stage-"diffusion" names (mld.py:137-139); `x_loss` is 0.0."""
+        st = self.sums()
+        out = {loss: 0.0 for loss in self.losses}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for name, s in zip(_DIFF_COMPUTED, st["sums"]):
+                out[name] = float(s / np.float64(st["count"]))
+        return out

@@ -133,7 +133,9 @@ class LADiffDenoiser(_HipModule):
     # ------------------------------------------------------------------
     def forward(self, sample, timestep, encoder_hidden_states, enclat=None, enclat_future=None, lengths=None,
                 latent_idx=None, max_iter_elements=None, **kwargs):
-        """sample [B2,T,256], timestep 0-dim or [B2] (all equal), encoder_hidden_states [B2,1,768] -> (eps [B2,T,256],)"""
+        """sample [B2,T,256], timestep 0-dim or [B2], encoder_hidden_states [B2,1,768] -> (eps [B2,T,256],).  A scalar or all-equal
+        timestep is the sampling loop's case (`ladiff_denoiser_forward`); a [B2] timestep with unequal values - every caller outside the
+        loop, `LADIFF._diffusion_process` first - runs `ladiff_denoiser_forward_timesteps` (one text token)."""
         if enclat is not None or enclat_future is not None:
             raise NotImplementedError("autoregressive conditioning (ARDIFF) is not built")
         n_text = int(encoder_hidden_states.shape[1])
@@ -143,14 +145,17 @@ class LADiffDenoiser(_HipModule):
         if Dm != self.latent_dim or T > _lib.MAX_LATENTS:
             raise ValueError(f"unsupported sample shape {tuple(sample.shape)}")
         t = torch.as_tensor(timestep).reshape(-1)
-        if t.numel() > 1 and not bool((t == t[0]).all()):
-            raise NotImplementedError("per-sample timesteps are not built (the sampling loop uses one t per call)")
+        per_sample = t.numel() > 1 and not bool((t == t[0]).all())
+        if per_sample and t.numel() != B2:
+            raise ValueError(f"timestep has {t.numel()} different values for {B2} samples")
         wt = self._weight_table()
         x = sample.detach().to(torch.float32).contiguous()
         text = encoder_hidden_states.detach().to(torch.float32).contiguous()
         counts = None
         if max_iter_elements is not None and not self.test_efficiency:
             counts = torch.as_tensor(max_iter_elements).to(device=dev, dtype=torch.int32).contiguous()
+        if per_sample:
+            return (self._forward_timesteps(wt, x, t, text, counts).to(sample.dtype),)
         sinus = timestep_sinusoid(t[:1].cpu(), self.text_encoded_dim).to(dev)
         tables = torch.empty(L.ladiff_denoiser_tables_floats(1), dtype=torch.float32, device=dev)
         cache = torch.empty(L.ladiff_denoiser_text_cache_floats(B2, 1, n_text), dtype=torch.float32, device=dev)
@@ -167,6 +172,23 @@ class LADiffDenoiser(_HipModule):
                                              B2, 1, T, None if counts is None else counts.data_ptr(), _lib.ptr(eps),
                                              _lib.ptr(ws), wsb, st))
         return (eps.to(sample.dtype),)
+
+    def _forward_timesteps(self, wt, x, t, text, counts):
+        """`ladiff_denoiser_forward_timesteps` on contiguous fp32 device tensors: x [B2,T,256], t [B2] (any integer dtype, any device),
+        text [B2,1,768], counts int32 [B2] or None.  The entry builds its per-sample tables inside the one workspace."""
+        L = _lib.lib()
+        B2, T, _ = x.shape
+        if text.shape[1] != 1:
+            raise NotImplementedError("per-sample timesteps with more than one text token are not built")
+        ts = t.to(device=x.device, dtype=torch.int64).contiguous()
+        wsb = L.ladiff_denoiser_forward_timesteps_workspace_bytes(B2, T)
+        ws = _lib.workspace(wsb, x.device)
+        eps = torch.empty_like(x)
+        _lib.check(L.ladiff_denoiser_forward_timesteps(wt.array, wt.split_array() if _lib.is_split(self.precision) else None,
+                                                       _lib.ptr(text), 1, ts.data_ptr(), _lib.ptr(x), B2, T,
+                                                       None if counts is None else counts.data_ptr(), _lib.ptr(eps), _lib.ptr(ws), wsb,
+                                                       _lib.stream_ptr()))
+        return eps
 
 
 class LADiffVae(_HipModule):

@@ -97,7 +97,8 @@ class _Scheduler:
         return SchedulerOutput(out.to(sample.dtype))
 
     def add_noise(self, original_samples, noise, timesteps):
-        """x_t = sqrt(a_t) x_0 + sqrt(1 - a_t) eps  (training side, ladiff.py:776; plain torch, not on the hot path)."""
+        """x_t = sqrt(a_t) x_0 + sqrt(1 - a_t) eps  (ladiff.py:776) in plain torch, for callers that hold a scheduler alone;
+        `LADIFF.train_diffusion_forward` runs `ladiff_q_sample` instead (one launch, with the permute and the LAD zeroing)."""
         a = self.alphas_cumprod.to(original_samples.device)[timesteps.to(original_samples.device)]
         a = a.to(original_samples.dtype)
         while a.dim() < original_samples.dim():
