@@ -397,8 +397,11 @@ LADIFF_API int ladiff_vae_decode_graphed(void* graph, const float* const* w, con
 /* ------------------------------------------------------------------ LA-VAE encoder
  * LADiffVae.encode, ladiff_vae.py:162-286 (call sites ladiff.py:269, :324, :1096): features[B,F,C] ->
  * mu, std, latent, each [T,B,256] (sequence-first like the reference); latent = mu + std * eps with rows >= counts[b]
- * zeroed; eps[T,B,256] stands in for the draw inside Normal.rsample().  F + 2T <= 224.  Weight table as for the
- * decoder: ladiff_encoder_param_name(i) lists the state-dict keys. */
+ * zeroed; eps[T,B,256] stands in for the draw inside Normal.rsample().  Limits: F >= 1, 1 <= T <= LADIFF_MAX_LATENTS, C >= 1 and
+ * 3 <= F + 2T <= LADIFF_MAX_FRAMES (the sequence [T mu tokens | T logvar tokens | F frames] is one attention of at most 224 keys;
+ * sequences of fewer than 8 rows are served like any other); LADIFF_ERR_SHAPE otherwise, before anything is queued.  B == 0 is a no-op.
+ * lengths[b] in [1, F] and counts[b] in [1, T] are the caller's to keep: they only select keys.  Weight table as for the decoder:
+ * ladiff_encoder_param_name(i) lists the state-dict keys. */
 LADIFF_API int ladiff_encoder_num_params(void);
 LADIFF_API const char* ladiff_encoder_param_name(int i);
 LADIFF_API size_t ladiff_encoder_workspace_bytes(int B, int F, int T, int C);

@@ -441,12 +441,16 @@ __global__ __launch_bounds__(256) void encoder_assemble_kernel(const float* __re
             if (ok) w |= 1u << (k & 31);
         }
         keybits[(size_t)b * 8 + sq] = w;
+        // S < 8 (T = 1 with <= 5 frames, ..., T = 3 with 1 frame): the sample's last row writes the words no row is left for (keys >= S: 0)
+        if (sq == S - 1)
+            for (int i = S; i < 8; ++i) keybits[(size_t)b * 8 + i] = 0;
     }
 }
 int launch_encoder_assemble(const float* token, const float* emb, const float* pe, const int32_t* lengths,
                             const int32_t* counts, int B, int F, int T, float* x, float* xs, uint32_t* keybits, hipStream_t s) {
     const int S = 2 * T + F, M = B * S;
-    if (S < 8) return LADIFF_ERR_SHAPE;
+    if (F < 1 || T < 1) return LADIFF_ERR_SHAPE;
+    if (M == 0) return 0;
     hipLaunchKernelGGL(encoder_assemble_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, token, emb, pe,
                        lengths, counts, F, 2 * T, S, M, x, xs, keybits);
     LADIFF_LAUNCH_CHECK();

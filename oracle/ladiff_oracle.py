@@ -472,11 +472,13 @@ def detr_encoder_layer(x, p, key_pad):
     return layer_norm(x + f, p["norm2.weight"], p["norm2.bias"])
 
 
-def vae_encode(sd, features, lengths, eps, max_it=5, frame_per_latent=48, num_layers=9):
+def vae_encode(sd, features, lengths, eps, max_it=5, frame_per_latent=48, num_layers=9, key_lengths=None):
     """LADiffVae.encode, LAD / mld-PE branch (ladiff_vae.py:162-286).  features [B,F,C] -> (mu, std, latent), each
-    [max_it,B,D]; `eps` [max_it,B,D] stands in for Normal.rsample's draw.  Pinned by tests/golden/vae_encode_*.npz."""
+    [max_it,B,D]; `eps` [max_it,B,D] stands in for Normal.rsample's draw.  Pinned by tests/golden/vae_encode_*.npz.
+    `key_lengths` (tests only) builds the frame-key mask from other lengths than the latent counts: what a wrongly admitted or
+    dropped frame key does to the result (tests/test_encoder_cases.py)."""
     B, Fr, _ = features.shape
-    mask = lengths_to_mask(lengths, Fr)                                                  # :178
+    mask = lengths_to_mask(lengths if key_lengths is None else key_lengths, Fr)          # :178
     x = linear(features, sd["skel_embedding.weight"], sd["skel_embedding.bias"])         # :182
     tok = sd["global_motion_token"][None].expand(B, -1, -1)                              # :189
     counts = max_iter_elements(lengths, frame_per_latent)                                # :198

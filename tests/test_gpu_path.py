@@ -440,7 +440,8 @@ def test_forward_uses_device_feats2joints(denoiser, vae):
 
 # ---------------------------------------------------------------- LA-VAE encode (next row)
 @pytest.mark.parametrize("name,nfeats,precision", [("vae_encode_humanml", 263, "fp32"), ("vae_encode_kit", 251, "fp32"),
-                                                   ("vae_encode_humanml", 263, "f16x3")])
+                                                   ("vae_encode_humanml", 263, "f16x3"), ("vae_encode_edges", 251, "fp32"),
+                                                   ("vae_encode_edges", 251, "f16x3")])
 def test_vae_encode_golden(name, nfeats, precision):
     g = load_golden(name)
     v = make_vae(nfeats)

@@ -110,9 +110,10 @@ def test_feats2joints(name):
     assert j.shape == g["joints"].shape and maxdiff(j, g["joints"]) < 1e-6
 
 
-@pytest.mark.parametrize("name,nfeats", [("vae_encode_humanml", 263), ("vae_encode_kit", 251)])
+@pytest.mark.parametrize("name,nfeats", [("vae_encode_humanml", 263), ("vae_encode_kit", 251), ("vae_encode_edges", 251)])
 def test_vae_encode(name, nfeats):
-    """Next row of the scope table, pinned to the reference's LADiffVae.encode."""
+    """Next row of the scope table, pinned to the reference's LADiffVae.encode.  vae_encode_edges: lengths 1, 47, 48, 49,
+    96, 97 (length 1 and both sides of two latent-count boundaries), which tests/test_gpu_encoder_shapes.py relies on the oracle for."""
     g = load_golden(name)
     mu, std, latent = orc.vae_encode(syn.vae_weights(nfeats), g["features"], g["lengths"].tolist(), g["eps"])
     assert maxdiff(mu, g["mu"]) < TOL and maxdiff(std, g["std"]) < TOL and maxdiff(latent, g["latent"]) < TOL
