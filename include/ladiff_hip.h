@@ -448,9 +448,11 @@ LADIFF_API int ladiff_vae_losses(const float* m_rst, const float* m_ref, const f
  * text token (n_text != 1: LADIFF_ERR_UNSUPPORTED), counts[B2] latent counts or NULL, both arithmetic modes (w_split NULL = fp32).  Unlike
  * ladiff_denoiser_forward it takes no tables, step counter or text cache: those are per CALL there and per SAMPLE here, so the entry
  * builds them in its workspace - the sinusoid and the time tables with row b = sample b's timestep, the step-invariant text cache, and a
- * "diagonal" c table [9][B2][valid | pad][256] (the padded rows' vector depends on the sample's timestep too) - and the three row kernels
- * that read the step counter in the loop read table row b instead.  The launch count does not depend on B2 and the workspace is O(B2 T).
- * f16x3 mode runs the unfused sequence (split-operand GEMMs + row kernels that write the S-format twin).  With equal timesteps the result
+ * "diagonal" c table [9][B2][valid | pad][256] (the padded rows' vector depends on the sample's timestep too) - and then runs
+ * ladiff_denoiser_forward's own layer sequence.  The three row kernels that read the step counter there are shared: their per-sample
+ * instantiations (den_self_attn_kernel<T, true>, reduce_rows_kernel<true>) read table row b instead, the loop and ladiff_denoiser_forward
+ * run the <.., false> ones.  The launch count does not depend on B2 and the workspace is O(B2 T).  f16x3 mode runs the unfused sequence
+ * (split-operand GEMMs + row kernels that write the S-format twin; the two fused kernels read the step counter).  With equal timesteps the result
  * equals ladiff_denoiser_forward's within the fp32 gate (5e-6 measured in both modes; not bit for bit: the time-table GEMMs run on B2
  * rows here and on one row there, and the f16x3 kernels differ).  All pointers 16-byte aligned
  * (timesteps 8, counts 4): LADIFF_ERR_SHAPE otherwise and for T outside 1 .. LADIFF_MAX_LATENTS.  The query is non-decreasing.

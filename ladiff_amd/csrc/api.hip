@@ -113,8 +113,10 @@ int ladiff_combine_rows(const float* partials, int n_planes, int M, const float*
     if (mode != RED_PLAIN && !(ln_gamma && ln_beta)) return LADIFF_ERR_ARG;
     if ((mode == RED_LN_ADD || mode == RED_LN_MOD) && !table) return LADIFF_ERR_ARG;
     if (M == 0) return 0;
-    return launch_reduce_rows(partials, n_planes, M, bias, res, mode, ln_gamma, ln_beta, table, 0, nullptr, counts, Bs, T,
-                              pad_row, 0, out, nullptr, S(stream));
+    RedArgs r;
+    r.P = partials; r.S = n_planes; r.M = M; r.bias = bias; r.res = res; r.mode = mode; r.g = ln_gamma; r.b = ln_beta; r.tab = table;
+    r.counts = counts; r.Bs = Bs; r.T = T; r.pad_row = pad_row; r.out = out;
+    return launch_reduce_rows(r, S(stream));
 }
 
 int ladiff_layernorm(const float* x, const float* gamma, const float* beta, float* y, int M, ladiff_stream_t stream) {

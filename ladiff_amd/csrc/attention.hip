@@ -479,8 +479,9 @@ int launch_decoder_cross_attention(const float* q, const float* kv, const int32_
 // sa_block attention of LinearTemporalDiffusionTransformerDecoderLayer (mdiff_transformer.py:296-313): queries
 // are the T latent rows; keys/values are [T latent rows | text token | time token]; latent keys >= counts[b]
 // are masked, the two extra tokens never are.  The text token's K|V are step-invariant (text cache) and the
-// time token's K|V depend on (step, layer) only (time table).  One workgroup per sample, wave = head, lane = d.
-template <int T>
+// time token's K|V depend on (step, layer) only (time table): row *d_step of `tables`, or - PER_SAMPLE, one timestep per sample
+// (diffusion_stage.hip) - row bg.  One workgroup per sample, wave = head, lane = d.
+template <int T, bool PER_SAMPLE>
 __global__ __launch_bounds__(256) void den_self_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ text_kv,
                                                             const float* __restrict__ tables, int kv_off, int step_stride,
                                                             const int32_t* __restrict__ d_step,
@@ -499,7 +500,7 @@ __global__ __launch_bounds__(256) void den_self_attn_kernel(const float* __restr
     }
     kk[T] = text_kv[(size_t)bg * 512 + col];
     vv[T] = text_kv[(size_t)bg * 512 + 256 + col];
-    const float* tk = tables + (size_t)(*d_step) * step_stride + kv_off;
+    const float* tk = tables + (size_t)(PER_SAMPLE ? bg : *d_step) * step_stride + kv_off;
     kk[T + 1] = tk[col];
     vv[T + 1] = tk[256 + col];
     int nv = counts ? counts[bg % Bs] : T;
@@ -541,8 +542,12 @@ int launch_denoiser_self_attention(const float* qkv, const float* text_kv, const
     const dim3 grid(b_n), block(256);
 #define LADIFF_SA_CASE(TT)                                                                                          \
     case TT:                                                                                                        \
-        hipLaunchKernelGGL(den_self_attn_kernel<TT>, grid, block, 0, s, qkv, text_kv, tables, kv_off, step_stride, \
-                           d_step, counts, Bs, b_off, out, split_out);                                                                \
+        if (d_step == nullptr)                                                                                      \
+            hipLaunchKernelGGL((den_self_attn_kernel<TT, true>), grid, block, 0, s, qkv, text_kv, tables, kv_off,    \
+                               step_stride, d_step, counts, Bs, b_off, out, split_out);                               \
+        else                                                                                                        \
+            hipLaunchKernelGGL((den_self_attn_kernel<TT, false>), grid, block, 0, s, qkv, text_kv, tables, kv_off,   \
+                               step_stride, d_step, counts, Bs, b_off, out, split_out);                               \
         break;
     switch (T) {
         LADIFF_SA_CASE(1) LADIFF_SA_CASE(2) LADIFF_SA_CASE(3) LADIFF_SA_CASE(4)

@@ -102,11 +102,10 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         }
         g.split = 1;
         LADIFF_TRY(launch_gemm(g, s));
-        if (n2)      // norm3, then decoder.norm: one row pass
-            return launch_reduce_rows(dst, 1, M, nullptr, nullptr, RED_LN, n1.g, n1.b, nullptr, 0, nullptr, nullptr, 1, 1, 0,
-                                      0, dst, dsts, s, nullptr, n2->g, n2->b);
-        return launch_reduce_rows(dst, 1, M, nullptr, nullptr, RED_LN, n1.g, n1.b, nullptr, 0, nullptr, nullptr, 1, 1, 0, 0,
-                                  dst, dsts, s);
+        RedArgs r;
+        r.P = dst; r.M = M; r.mode = RED_LN; r.g = n1.g; r.b = n1.b; r.out = dst; r.outs = dsts;
+        if (n2) { r.g2 = n2->g; r.b2 = n2->b; }      // norm3, then decoder.norm: one row pass
+        return launch_reduce_rows(r, s);
     };
 
     // queries = zeros + query_pos_decoder.pe[:F]     ladiff_vae.py:299, :334
@@ -192,8 +191,11 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
             LADIFF_TRY(krs(Ps[2], D, Ls.lin1.w, L.lin1.b, nullptr, hid, FF, FF, ACT_GELU, nullptr, M)); DEC_CUT();
             // linear2: K = 1024 as four partial planes (the q|k|v + attention buffers are free by now), summed by the LayerNorm pass
             LADIFF_TRY(krs(hid, FF, Ls.lin2.w, nullptr, qkv, nullptr, D, D, ACT_NONE, nullptr, M)); DEC_CUT();
-            LADIFF_TRY(launch_reduce_rows(qkv, 4, M, L.lin2.b, P[2], RED_LN, L.norm3.g, L.norm3.b, nullptr, 0, nullptr, nullptr, 1, 1, 0, 0,
-                                          dst, dsts, s, nullptr, last ? w.norm.g : nullptr, last ? w.norm.b : nullptr));
+            RedArgs r;
+            r.P = qkv; r.S = 4; r.M = M; r.bias = L.lin2.b; r.res = P[2]; r.mode = RED_LN; r.g = L.norm3.g; r.b = L.norm3.b;
+            r.out = dst; r.outs = dsts;
+            if (last) { r.g2 = w.norm.g; r.b2 = w.norm.b; }
+            LADIFF_TRY(launch_reduce_rows(r, s));
         } else {
             GemmArgs g = lin(sp ? Ps[2] : P[2], D, Ls.lin1.w, L.lin1.b, sp ? nullptr : hid, FF, M, FF, D, ACT_GELU);
             g.split = sp ? 1 : 0; if (sp) g.Ys = hid;

@@ -73,13 +73,6 @@ const std::vector<std::string>& encoder_param_names() {
     return names;
 }
 
-// ------------------------------------------------------------------ small GEMM helper
-static GemmArgs lin(const float* A, int lda, const LinearW& l, float* Y, int ldy, int M, int N, int K, int act = ACT_NONE) {
-    GemmArgs g;
-    g.A = A; g.lda = lda; g.W = l.w; g.ldw = K; g.bias = l.b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
-    return g;
-}
-
 // ------------------------------------------------------------------ time tables
 int denoiser_time_tables(const DenoiserW& w, const float* sinus, int n, float* tables, float* ws, size_t ws_floats,
                          hipStream_t s) {
@@ -244,11 +237,6 @@ int linear_cross_attention(const DenoiserW& w, int layer, const float* x, const 
 // f16x3 mode (8 launches, 9 on the output blocks): the same arithmetic with the steps grouped into fused kernels -
 //   [skip] gemm_rowln (concat GEMM + bias) | qkv_attn (qkv + att) | gemm_rowln (R1, X1) | linear1 | linear2 split-K |
 //   reduce_rows (X3) | ffn.linear1 | ffn.linear2 split-K | combine_gemm (u, x').
-static KrArgs kr(const float* A, int lda, const float* W, const float* b, float* Y, int ldy, int M, int N, int K, int act = ACT_NONE) {
-    KrArgs g;
-    g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
-    return g;
-}
 
 // Processes samples [b_lo, b_lo + b_n) of the duplicated batch of B2 = Bs * dup samples (tables / caches are sized for
 // B2); independent sample ranges can run concurrently on different streams with disjoint workspaces.
@@ -257,10 +245,17 @@ static KrArgs kr(const float* A, int lda, const float* W, const float* b, float*
 // ws != nullptr selects the f16x3 matrix path: `ws` holds the S-format copies of the weight matrices (same table order
 // as `w`), GEMM operands travel in S-format (every tensor that is both a GEMM operand and a residual is written twice:
 // fp32 for the residual / LayerNorm consumers, S-format for the MFMA), accumulation and everything else stay fp32.
+//
+// d_step == nullptr: one timestep per SAMPLE (denoiser_forward_timesteps).  The three row operations that read a table row - the
+// time token's K|V, the c row added after norm2, the FFN's (scale | shift) - take row b2 of `tables` / `dctab` instead of row
+// *d_step (their PER_SAMPLE instantiations); qkv_attn.hip and combine_gemm read *d_step, so f16x3 mode runs their unfused halves.
 int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tables, const int32_t* d_step, const float* cache,
                      int n_steps, const float* sample, int Bs, int dup, int T, const int32_t* counts, float* eps, float* ws,
-                     size_t ws_floats, hipStream_t s, int b_lo, int b_n, int loop_mode, int ntxt, const int32_t* d_base) {
+                     size_t ws_floats, hipStream_t s, int b_lo, int b_n, int loop_mode, int ntxt, const int32_t* d_base,
+                     const float* dctab) {
     const int B2 = Bs * dup;
+    const bool per_sample = d_step == nullptr;
+    if (per_sample && (dctab == nullptr || ntxt != 1 || loop_mode)) return LADIFF_ERR_ARG;
     if (b_n < 0) { b_lo = 0; b_n = B2; }
     const int M = b_n * T;
     if (T < 1 || T > LADIFF_MAX_LATENTS || b_lo < 0 || b_lo + b_n > B2) return LADIFF_ERR_SHAPE;
@@ -278,6 +273,13 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
     const int R = B2 + 1;
     // operand view of a tensor: its S-format twin in the f16x3 path, the fp32 tensor otherwise
     auto gemm = [&](KrArgs g) { g.split = sp ? 1 : 0; return launch_gemm_kr(g, s); };
+    // combine of S planes of `src` (+ bias, + res), LayerNorm n (or none: RED_PLAIN) -> out / outs; the caller adds what its mode reads
+    auto red = [&](const float* src, int S, const float* bias, const float* res, const NormW* n, float* out, float* outs) {
+        RedArgs r;
+        r.P = src; r.S = S; r.M = M; r.bias = bias; r.res = res; r.out = out; r.outs = outs;
+        if (n != nullptr) { r.mode = RED_LN; r.g = n->g; r.b = n->b; }
+        return r;
+    };
 
     // x = cat([sample]*dup) + query_pos.pe[:T]        ladiff.py:472-474, ladiff_denoiser.py:251
     // loop_mode: the caller's step-tail kernel has already written x into P[0] / Ps[0] and will apply encoder.norm itself
@@ -300,13 +302,12 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
                 KrArgs g = kr(cur, D, sks.w, nullptr, part, D, M, D, 2 * D);
                 g.A2 = SK[NL - 1 - l]; g.lda2 = D; g.K1 = D;
                 LADIFF_TRY(gemm(g));
-                LADIFF_TRY(launch_reduce_rows(part, 2, M, sk.b, nullptr, RED_PLAIN, nullptr, nullptr, nullptr, 0, nullptr,
-                                              nullptr, 1, 1, 0, 0, P[3], Ps[3], s));
+                LADIFF_TRY(launch_reduce_rows(red(part, 2, sk.b, nullptr, nullptr, P[3], Ps[3]), s));
             }
             cur = P[3]; curs = Ps[3];
         }
         const float* att_op = att;                    // the attention output as out_proj's operand
-        if (sp && ntxt == 1) {   // in_proj + attention core in one launch (qkv_attn.hip)
+        if (sp && ntxt == 1 && !per_sample) {   // in_proj + attention core in one launch (qkv_attn.hip)
             LADIFF_TRY(launch_qkv_attention(curs, Ls.sa_attn.in_w, L.sa_attn.in_b, tkv + (size_t)l * B2 * 2 * D, tl,
                                             DEN_OFF_TIME_KV, DEN_STEP_STRIDE, d_step, counts, Bs, b_lo, b_n, T, att, s));
         } else {
@@ -317,9 +318,9 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
                 LADIFF_TRY(launch_denoiser_self_attention_general(qkv, tkv + (size_t)l * B2 * ntxt * 2 * D, ntxt, tl, DEN_OFF_TIME_KV,
                                                                   DEN_STEP_STRIDE, d_step, counts, Bs, b_lo, b_n, T, att, s));
                 if (sp) { LADIFF_TRY(launch_split_rows(att, hid, M, D, s)); att_op = hid; }
-            } else
+            } else      // f16x3 (per-sample step only): written as out_proj's S-format operand
                 LADIFF_TRY(launch_denoiser_self_attention(qkv, tkv + (size_t)l * B2 * 2 * D, tl, DEN_OFF_TIME_KV, DEN_STEP_STRIDE,
-                                                          d_step, counts, Bs, b_lo, b_n, T, att, 0, s));
+                                                          d_step, counts, Bs, b_lo, b_n, T, att, sp ? 1 : 0, s));
         }
         if (sp) {   // X1 = LN1(x + out_proj(att)) -> P[2] / Ps[2], one launch (gemm_rowln.hip)
             RowLnArgs g;
@@ -332,8 +333,7 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
             g.res = cur; g.ldres = D;
             LADIFF_TRY(gemm(g));
             // X1 = LN1(R1) -> P[2]
-            LADIFF_TRY(launch_reduce_rows(P[1], 1, M, nullptr, nullptr, RED_LN, L.sa_norm1.g, L.sa_norm1.b, nullptr, 0, nullptr,
-                                          nullptr, 1, 1, 0, 0, P[2], Ps[2], s));
+            LADIFF_TRY(launch_reduce_rows(red(P[1], 1, nullptr, nullptr, &L.sa_norm1, P[2], Ps[2]), s));
         }
         // hid = relu(linear1(X1))
         {
@@ -348,10 +348,8 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
             // literal LinearTemporalCrossAttention (mdiff_transformer.py:219-247): X2 = LN2(..) -> P[1]; q = query(LN(X2));
             // u = SiLU(AdaLN(LN(softmax_d(q) . att_b)));  X3 = X2 + out(u) -> first M x 256 of the qkv buffer
             // f16x3 mode: the two projections run on S-format operands (3 bf16 MFMAs per product), softmax / LayerNorm / AdaLN fp32
-            LADIFF_TRY(launch_reduce_rows(part, 4, M, L.sa_lin2.b, P[2], RED_LN, L.sa_norm2.g, L.sa_norm2.b, nullptr, 0, nullptr,
-                                          nullptr, 1, 1, 0, 0, P[1], nullptr, s));
-            if (sp) LADIFF_TRY(launch_reduce_rows(P[1], 1, M, nullptr, nullptr, RED_LN, L.ca_norm.g, L.ca_norm.b, nullptr, 0, nullptr,
-                                                  nullptr, 1, 1, 0, 0, P[2], Ps[2], s));
+            LADIFF_TRY(launch_reduce_rows(red(part, 4, L.sa_lin2.b, P[2], &L.sa_norm2, P[1], nullptr), s));
+            if (sp) LADIFF_TRY(launch_reduce_rows(red(P[1], 1, nullptr, nullptr, &L.ca_norm, P[2], Ps[2]), s));
             else LADIFF_TRY(launch_layernorm(P[1], L.ca_norm.g, L.ca_norm.b, P[2], M, s));
             LADIFF_TRY(gemm(kr(sp ? Ps[2] : P[2], D, Ls.ca_query.w, L.ca_query.b, att, D, M, D, D)));
             LADIFF_TRY(launch_lca_apply(att, ctab + (size_t)l * B2 * H * DH * DH, counts, Bs, b_lo, b_n, T, tl + DEN_OFF_CA_MOD,
@@ -362,8 +360,12 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
             LADIFF_TRY(gemm(g));
             x3 = qkv;
         } else {
-            LADIFF_TRY(launch_reduce_rows(part, 4, M, L.sa_lin2.b, P[2], RED_LN_ADD, L.sa_norm2.g, L.sa_norm2.b,
-                                          ctab + (size_t)l * n_steps * R * D, R * D, d_step, counts, Bs, T, B2, b_lo, P[1], Ps[1], s, d_base));
+            // the c row of (step, sample | pad): row *d_step - *d_base of [n_steps][B2 + 1], or - per sample - of dctab[b2][valid | pad]
+            RedArgs r = red(part, 4, L.sa_lin2.b, P[2], &L.sa_norm2, P[1], Ps[1]);
+            r.mode = RED_LN_ADD; r.counts = counts; r.Bs = Bs; r.T = T; r.b_off = b_lo;
+            if (per_sample) { r.tab = dctab + (size_t)l * B2 * 2 * D; r.tab_step_stride = 2 * D; r.pad_row = 1; }
+            else { r.tab = ctab + (size_t)l * n_steps * R * D; r.tab_step_stride = R * D; r.pad_row = B2; r.d_step = d_step; r.d_base = d_base; }
+            LADIFF_TRY(launch_reduce_rows(r, s, per_sample));
         }
         // u = SiLU(AdaLN(ffn.linear2(gelu(ffn.linear1(X3))))) -> P[2]
         {
@@ -374,7 +376,7 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
         LADIFF_TRY(gemm(kr(hid, FF, Ls.ffn2.w, nullptr, part, D, M, D, FF)));
         float* dst = is_in ? SK[l] : P[0];
         float* dsts = is_in ? SKs[l] : Ps[0];
-        if (sp) {   // combine + StylizationBlock + out projection + residual in one launch (gemm_rowln.hip)
+        if (sp && !per_sample) {   // combine + StylizationBlock + out projection + residual in one launch (gemm_rowln.hip)
             CombineGemmArgs g;
             g.P = part; g.plane = MD; g.S = 4; g.bias2 = L.ffn2.b; g.ln_g = L.ffn_proj.norm.g; g.ln_b = L.ffn_proj.norm.b;
             g.tab = tl + DEN_OFF_FFN_MOD; g.tab_step_stride = DEN_STEP_STRIDE; g.d_step = d_step;
@@ -382,10 +384,13 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
             g.Y = dst; g.Ys = dsts; g.ldy = D; g.M = M;
             LADIFF_TRY(launch_combine_gemm(g, s));
         } else {
-            LADIFF_TRY(launch_reduce_rows(part, 4, M, L.ffn2.b, nullptr, RED_LN_MOD, L.ffn_proj.norm.g, L.ffn_proj.norm.b,
-                                          tl + DEN_OFF_FFN_MOD, DEN_STEP_STRIDE, d_step, nullptr, 1, 1, 0, 0, P[2], nullptr, s));
+            // (scale | shift) of row *d_step, or - per sample - of row b2
+            RedArgs r = red(part, 4, L.ffn2.b, nullptr, &L.ffn_proj.norm, P[2], Ps[2]);
+            r.mode = RED_LN_MOD; r.tab = tl + DEN_OFF_FFN_MOD; r.tab_step_stride = DEN_STEP_STRIDE; r.d_step = d_step;
+            if (per_sample) { r.T = T; r.b_off = b_lo; }
+            LADIFF_TRY(launch_reduce_rows(r, s, per_sample));
             // x' = X3 + out_layers(u)
-            KrArgs g = kr(P[2], D, Ls.ffn_proj.out.w, L.ffn_proj.out.b, dst, D, M, D, D);
+            KrArgs g = kr(sp ? Ps[2] : P[2], D, Ls.ffn_proj.out.w, L.ffn_proj.out.b, dst, D, M, D, D);
             g.res = x3; g.ldres = D; g.Ys = dsts;
             LADIFF_TRY(gemm(g));
         }

@@ -41,14 +41,14 @@ int vae_encode(const EncoderW& w, const EncoderW* wsp, const float* features, co
         }
         g.split = 1;
         LADIFF_TRY(launch_gemm(g, s));
+        RedArgs r;      // LayerNorm in place, the S-format twin written by the last pass
+        r.P = dst; r.M = M; r.mode = RED_LN; r.g = n1.g; r.b = n1.b; r.out = dst;
         if (n2) {
-            LADIFF_TRY(launch_reduce_rows(dst, 1, M, nullptr, nullptr, RED_LN, n1.g, n1.b, nullptr, 0, nullptr, nullptr, 1, 1, 0,
-                                          0, dst, nullptr, s));
-            return launch_reduce_rows(dst, 1, M, nullptr, nullptr, RED_LN, n2->g, n2->b, nullptr, 0, nullptr, nullptr, 1, 1, 0,
-                                      0, dst, dsts, s);
+            LADIFF_TRY(launch_reduce_rows(r, s));
+            r.g = n2->g; r.b = n2->b;
         }
-        return launch_reduce_rows(dst, 1, M, nullptr, nullptr, RED_LN, n1.g, n1.b, nullptr, 0, nullptr, nullptr, 1, 1, 0, 0,
-                                  dst, dsts, s);
+        r.outs = dsts;
+        return launch_reduce_rows(r, s);
     };
 
     // x = skel_embedding(features)  (K = nfeats is padded to a multiple of 32 columns)            ladiff_vae.py:182

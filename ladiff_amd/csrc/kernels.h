@@ -7,10 +7,24 @@ namespace ladiff {
 
 // rowops.hip
 enum RedMode : int { RED_PLAIN = 0, RED_LN = 1, RED_LN_ADD = 2, RED_LN_MOD = 3 };
-int launch_reduce_rows(const float* P, int S, int M, const float* bias, const float* res, int mode, const float* g,
-                       const float* b, const float* tab, int tab_step_stride, const int32_t* d_step,
-                       const int32_t* counts, int Bs, int T, int pad_row, int b_off, float* out, float* outs, hipStream_t s,
-                       const int32_t* d_base = nullptr, const float* g2 = nullptr, const float* b2 = nullptr);   // g2 / b2: RED_LN twice
+// reduce_rows_kernel's arguments (the kernel takes the struct as it is: the field order is its kernarg layout).  A caller sets what its
+// mode reads; row `row` belongs to sample b2 = b_off + row / T of the duplicated batch, whose latent count is counts[b2 % Bs].
+struct RedArgs {
+    const float* P = nullptr;                 // S planes of [M][256], `plane` floats apart
+    const float* bias = nullptr; const float* res = nullptr;
+    const float* g = nullptr; const float* b = nullptr;               // LayerNorm (every mode but RED_PLAIN)
+    const float* tab = nullptr;               // RED_LN_ADD: c table, rows [sample | pad_row]; RED_LN_MOD: (scale | shift); table row 0
+    const int32_t* d_step = nullptr;          // table row = *d_step - *d_base, `tab_step_stride` floats apart (NULL = 0)
+    const int32_t* counts = nullptr;          // RED_LN_ADD: latent rows >= counts[..] take the pad row (NULL = none does)
+    float* out = nullptr; float* outs = nullptr;                      // fp32 result, S-format twin (each optional)
+    const int32_t* d_base = nullptr;          // RED_LN_ADD: the table's first row belongs to step *d_base (windowed c table)
+    const float* g2 = nullptr; const float* b2 = nullptr;             // RED_LN: a second LayerNorm on the result (the decoder's last layer: norm3, then decoder.norm)
+    size_t plane = 0;                         // = M * 256, filled by the launcher
+    int S = 1, mode = RED_PLAIN, tab_step_stride = 0, Bs = 1, T = 1, pad_row = 0, b_off = 0, M = 0;
+};
+// per_sample: the table row is the row's sample b2 instead of *d_step, and RED_LN_ADD's valid row is row 0 of it (pad_row = 1 and
+// tab_step_stride = 512 address a [B2][valid | pad][256] table)
+int launch_reduce_rows(const RedArgs& a, hipStream_t s, bool per_sample = false);
 int launch_split_rows(const float* x, float* y, int R, int K, hipStream_t s);
 int launch_gather_rows(const float* src, const int32_t* index, int n_rows, int row_floats, float* dst, hipStream_t s);
 int launch_split_range_stats(const float* const* xs, const int64_t* counts, int n, int64_t max_count, unsigned long long* stats,
@@ -94,6 +108,7 @@ int launch_vae_losses(const float* m_rst, const float* m_ref, size_t n_feat, con
                       double* batch, double* acc, hipStream_t s);
 
 // attention.hip
+// d_step == NULL: the time token's K|V of sample b come from table row b (one timestep per sample), not from row *d_step
 int launch_denoiser_self_attention(const float* qkv, const float* text_kv, const float* tables, int kv_off,
                                    int step_stride, const int32_t* d_step, const int32_t* counts, int Bs, int b_off,
                                    int b_n, int T, float* out, int split_out, hipStream_t s);

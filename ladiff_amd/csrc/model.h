@@ -12,14 +12,28 @@
 
 namespace ladiff {
 
+// argument builders of the two small-GEMM launchers: one dense [N][K] weight, activations with their own row strides
+inline GemmArgs lin(const float* A, int lda, const LinearW& l, float* Y, int ldy, int M, int N, int K, int act = ACT_NONE) {
+    GemmArgs g;
+    g.A = A; g.lda = lda; g.W = l.w; g.ldw = K; g.bias = l.b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
+    return g;
+}
+inline KrArgs kr(const float* A, int lda, const float* W, const float* b, float* Y, int ldy, int M, int N, int K, int act = ACT_NONE) {
+    KrArgs g;
+    g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
+    return g;
+}
+
 int denoiser_time_tables(const DenoiserW& w, const float* sinus, int n, float* tables, float* ws, size_t ws_floats, hipStream_t s);
 int denoiser_text_cache(const DenoiserW& w, const float* text, int B2, const float* tables, int n_steps, float* cache,
                         float* ws, size_t ws_floats, hipStream_t s, int ntxt = 1);
 int denoiser_forward(const DenoiserW& w, const DenoiserW* w_split, const float* tables, const int32_t* d_step,
                      const float* cache, int n_steps, const float* sample, int Bs, int dup, int T, const int32_t* counts, float* eps, float* ws,
                      size_t ws_floats, hipStream_t s, int b_lo = 0, int b_n = -1, int loop_mode = 0, int ntxt = 1,
-                     const int32_t* d_base = nullptr);
+                     const int32_t* d_base = nullptr, const float* dctab = nullptr);
 // n_steps = steps the c table inside `cache` covers; d_base (or NULL = 0) holds the step its first row belongs to
+// d_step == NULL: one timestep per SAMPLE - `tables` holds one row per sample of the batch and the c table is the diagonal
+// dctab [9][B2][valid | pad][256] (diffusion_stage.hip), not the one inside `cache`; one text token, no loop_mode
 int denoiser_text_static(const DenoiserW& w, const float* text, int B2, float* cache, float* ws, size_t ws_floats, hipStream_t s);
 int denoiser_ctab(const DenoiserW& w, const float* tables_lo, int n, float* cache, int B2, float* u, size_t u_floats, hipStream_t s,
                   const DenoiserW* w_split = nullptr);

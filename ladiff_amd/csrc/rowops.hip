@@ -67,15 +67,10 @@ int launch_layernorm(const float* x, const float* g, const float* b, float* y, i
 //   RED_LN      y = LN(x)                                          (norm1, mdiff_transformer.py:63)
 //   RED_LN_ADD  y = LN(x) + c[step][sample | pad]                  (norm2, then the hoisted ca_block: mdiff_transformer.py:66, :246)
 //   RED_LN_MOD  y = SiLU( LN(x) * (1 + scale_step) + shift_step )  (StylizationBlock of the FFN: mdiff_transformer.py:161-162)
-struct RedArgs {
-    const float* P; const float* bias; const float* res; const float* g; const float* b; const float* tab;
-    const int32_t* d_step; const int32_t* counts; float* out; float* outs;
-    const int32_t* d_base;            // RED_LN_ADD: the table's first row belongs to step *d_base (windowed c table), NULL = 0
-    const float* g2; const float* b2; // RED_LN: a second LayerNorm on the result (the decoder's last layer: norm3, then decoder.norm)
-    size_t plane;
-    int S, mode, tab_step_stride, Bs, T, pad_row, b_off, M;
-};
-
+// PER_SAMPLE (one timestep per sample, diffusion_stage.hip): the table row is the row's sample b2, not *d_step, and RED_LN_ADD's valid
+// row is row 0 of it - tab [B2][valid | pad][256] with pad_row = 1.  A template parameter, so that the scalar-step instantiation, which
+// the launch-per-stage loop replays 9 x steps times, stays the code it was; the order of the loads below is part of that.
+template <bool PER_SAMPLE>
 __global__ __launch_bounds__(256) void reduce_rows_kernel(const RedArgs p) {
     // all arguments are read in one go and pinned (common.h: pin_s): the kernel is a chain of latencies and a kernarg
     // re-read next to each use adds an s_load + wait per pointer
@@ -107,11 +102,12 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const RedArgs p) {
     int step = d_step != nullptr ? *(const __attribute__((address_space(1))) int32_t*)d_step : 0;
     if (d_base != nullptr) step -= *(const __attribute__((address_space(1))) int32_t*)d_base;
     const int b2 = b_off + row / T, tt = row % T;
+    if (PER_SAMPLE) step = b2;
     int cnt = 0x7fffffff;
     if (mode == RED_LN_ADD && counts != nullptr) cnt = *(const __attribute__((address_space(1))) int32_t*)(counts + b2 % Bs);
     const float* t = tab + (size_t)step * tab_step_stride;
     f32x4 t0 = zero, t1 = zero;
-    if (mode == RED_LN_ADD) { t0 = ld4g(t + (size_t)b2 * D + c); t1 = ld4g(t + (size_t)pad_row * D + c); }   // both candidates
+    if (mode == RED_LN_ADD) { t0 = ld4g(t + (size_t)(PER_SAMPLE ? 0 : b2) * D + c); t1 = ld4g(t + (size_t)pad_row * D + c); }   // both candidates
     else if (mode == RED_LN_MOD) { t0 = ld4g(t + c); t1 = ld4g(t + 256 + c); }
 
     f32x4 v;
@@ -140,17 +136,13 @@ __global__ __launch_bounds__(256) void reduce_rows_kernel(const RedArgs p) {
     if (outs != nullptr) store_split4g(outs + (size_t)row * D, c, v);
 }
 
-int launch_reduce_rows(const float* P, int S, int M, const float* bias, const float* res, int mode, const float* g,
-                       const float* b, const float* tab, int tab_step_stride, const int32_t* d_step,
-                       const int32_t* counts, int Bs, int T, int pad_row, int b_off, float* out, float* outs, hipStream_t s,
-                       const int32_t* d_base, const float* g2, const float* b2) {
-    if (S < 1 || S > 4) return LADIFF_ERR_SHAPE;       // split-K planes: K / 256 <= 4
-    RedArgs a;
-    a.g2 = g2; a.b2 = b2;
-    a.P = P; a.bias = bias; a.res = res; a.g = g; a.b = b; a.tab = tab; a.d_step = d_step; a.counts = counts; a.out = out;
-    a.outs = outs; a.plane = (size_t)M * D; a.S = S; a.mode = mode; a.tab_step_stride = tab_step_stride; a.Bs = Bs; a.T = T;
-    a.pad_row = pad_row; a.b_off = b_off; a.M = M; a.d_base = d_base;
-    hipLaunchKernelGGL(reduce_rows_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, a);
+int launch_reduce_rows(const RedArgs& args, hipStream_t s, bool per_sample) {
+    if (args.S < 1 || args.S > 4) return LADIFF_ERR_SHAPE;       // split-K planes: K / 256 <= 4
+    RedArgs a = args;
+    a.plane = (size_t)a.M * D;
+    const dim3 grid((a.M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), block(256);
+    if (per_sample) hipLaunchKernelGGL(reduce_rows_kernel<true>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(reduce_rows_kernel<false>, grid, block, 0, s, a);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }

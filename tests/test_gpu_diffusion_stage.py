@@ -107,10 +107,11 @@ def oracle_case(B, T, masked):
 
 
 @both
-@pytest.mark.parametrize("B,T,masked", [(1, 5, 1), (33, 5, 1), (6, 2, 0), (5, 8, 1)])
+@pytest.mark.parametrize("B,T,masked", [(1, 5, 1), (33, 5, 1), (6, 2, 0), (5, 8, 1), (2, 1, 1), (3, 3, 1)])
 def test_forward_shapes_against_the_oracle(denoiser, precision, B, T, masked):
     """B = 1; 165 rows with all timesteps distinct (no multiple of a row tile, across a 32- and a 64-row boundary); T = 2 without
-    counts; the largest T."""
+    counts; the largest T; T = 1, the smallest instantiation of the attention template and the shape at which row / T and row % T
+    degenerate; 9 rows of an odd T."""
     x, txt, ts, counts, want = oracle_case(B, T, masked)
     if B == 1:      # the module keeps a one-element timestep on the scalar entry: the new entry is called directly
         got = raw_forward_timesteps(denoiser, x.to(DEV), ts.to(DEV), txt.to(DEV), counts.to(device=DEV, dtype=torch.int32))
