@@ -358,6 +358,34 @@ LADIFF_API int ladiff_diffusion_reverse(void* sampler, const float* const* w, co
                              const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale,
                              float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z /*[T,B,256]*/,
                              void* ws, size_t ws_bytes, int reuse_time_tables, ladiff_stream_t stream);
+/* The same loop with the prompts of one batch as separate requests: a guidance scale and a noise key per prompt.
+ *   guidance_scales[b]: the scale of prompt b instead of `guidance_scale` (cfg != 0 only: LADIFF_ERR_ARG otherwise).  Every value is
+ *     simply evaluated, eps_u + g (eps_c - eps_u), also g <= 1.
+ *   seeds[b], prompt_index[b]: prompt b draws its per-step noise with Philox key seeds[b] and counter word 1 = prompt_index[b] (0 when
+ *     prompt_index is NULL) instead of the sampler's (seed, first_prompt + b): the same request gives the same motion whatever batch it
+ *     sits in and wherever in it.  Works without a sampler handle too.  prompt_index without seeds is LADIFF_ERR_ARG.
+ *   draw_init_noise != 0: the initial noise is drawn on the device as well - the same function at schedule position -1 (counter word
+ *     2 = 0xFFFFFFFF, which no schedule reaches) - so init_noise may be NULL; requires seeds (LADIFF_ERR_ARG otherwise).
+ *   A non-NULL step_noise or init_noise tensor still wins over the generator.
+ * The three arrays are DEVICE data: the call cannot check their values on the host, a non-finite scale gives non-finite latents for that
+ * prompt only, and a sampler keys them by POINTER - new values in the same buffers replay the captured graphs, a new buffer captures
+ * again.  All NULL and draw_init_noise = 0: exactly ladiff_diffusion_reverse (which forwards here). */
+LADIFF_API int ladiff_diffusion_reverse_prompts(void* sampler, const float* const* w, const float* const* w_split /*or NULL*/,
+                             uint64_t weights_generation, const float* text_emb /*[2B or B,n_text,768]*/,
+                             const float* init_noise /*[B,T,256], or NULL with draw_init_noise*/, const int32_t* counts /*[B] or NULL*/,
+                             const int32_t* final_counts /*[B] or NULL*/,
+                             const int32_t* h_counts /*HOST copy of counts, or NULL*/,
+                             const float* sinusoid /*[n,768]*/, const float* coef /*[n,8]*/,
+                             const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale,
+                             float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z /*[T,B,256]*/,
+                             void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales /*[B] device or NULL*/,
+                             const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
+                             int draw_init_noise, ladiff_stream_t stream);
+/* The per-prompt generator's values as a tensor: out[i][b][t][:] for schedule positions first_step + i of the prompt with key seeds[b]
+ * and index prompt_index[b]; first_step = -1 starts at the initial noise.  first_step < -1 is LADIFF_ERR_ARG. */
+LADIFF_API int ladiff_noise_fill_prompts(const uint64_t* seeds /*[B] device*/, const uint32_t* prompt_index /*[B] device or NULL*/,
+                             int first_step /* >= -1 */, int n_steps, int B, int T, float* out /*[n_steps,B,T,256]*/,
+                             ladiff_stream_t stream);
 
 /* ------------------------------------------------------------------ LA-VAE decoder (LADiffVae.decode)
  * feats[B,F,C] from z[T,B,256]; frames >= lengths[b] come out zero.  ladiff_vae.py:288-362

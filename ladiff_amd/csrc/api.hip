@@ -390,6 +390,15 @@ int ladiff_noise_fill(uint64_t seed, uint32_t first_prompt, int first_step, int 
                              S(stream));
 }
 
+int ladiff_noise_fill_prompts(const uint64_t* seeds, const uint32_t* prompt_index, int first_step, int n_steps, int B, int T, float* out,
+                              ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(out != nullptr && first_step >= -1 && n_steps >= 0 && B >= 0 && (seeds != nullptr || B == 0));
+    if (T < 1 || T > LADIFF_MAX_LATENTS) return LADIFF_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(seeds) & 7) || (reinterpret_cast<uintptr_t>(prompt_index) & 3)) return LADIFF_ERR_SHAPE;
+    return launch_noise_fill(NoiseGen{0u, 0u, 0u, 1, reinterpret_cast<const unsigned long long*>(seeds), prompt_index}, first_step, n_steps, B, T,
+                             out, S(stream));
+}
+
 int ladiff_sampler_set_fault(void* sampler, int workgroup, int timeout_ms) {
     Sampler* sp = reinterpret_cast<Sampler*>(sampler);
     LADIFF_CHECK_ARG(sp != nullptr && workgroup >= -1 && workgroup < 256 && timeout_ms >= 0);
@@ -456,14 +465,33 @@ int ladiff_diffusion_reverse(void* sampler, const float* const* w, const float* 
                              const int32_t* h_counts, const float* sinusoid, const float* coef, const float* step_noise, float guidance_scale,
                              float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z, void* ws, size_t ws_bytes,
                              int reuse_time_tables, ladiff_stream_t stream) {
+    return ladiff_diffusion_reverse_prompts(sampler, w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid,
+                                            coef, step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
+                                            reuse_time_tables, nullptr, nullptr, nullptr, 0, stream);
+}
+
+int ladiff_diffusion_reverse_prompts(void* sampler, const float* const* w, const float* const* w_split, uint64_t weights_generation,
+                                     const float* text_emb, const float* init_noise, const int32_t* counts, const int32_t* final_counts,
+                                     const int32_t* h_counts, const float* sinusoid, const float* coef, const float* step_noise,
+                                     float guidance_scale, float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z,
+                                     void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales, const uint64_t* seeds,
+                                     const uint32_t* prompt_index, int draw_init_noise, ladiff_stream_t stream) {
     DenoiserW W, WS;
-    LADIFF_CHECK_ARG(load_weights(W, w) && text_emb && init_noise && sinusoid && coef && z && ws && B > 0 && n_steps > 0);
+    // what the host can see of the per-prompt arguments, before anything touches the GPU (their VALUES are device data)
+    LADIFF_CHECK_ARG(guidance_scales == nullptr || cfg != 0);
+    LADIFF_CHECK_ARG(prompt_index == nullptr || seeds != nullptr);
+    LADIFF_CHECK_ARG(!draw_init_noise || seeds != nullptr);
+    LADIFF_CHECK_ARG(init_noise != nullptr || draw_init_noise);
+    LADIFF_CHECK_ARG(load_weights(W, w) && text_emb && sinusoid && coef && z && ws && B > 0 && n_steps > 0);
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
     if (T < 1 || T > LADIFF_MAX_LATENTS || n_text < 1) return LADIFF_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(guidance_scales) & 3) || (reinterpret_cast<uintptr_t>(seeds) & 7) ||
+        (reinterpret_cast<uintptr_t>(prompt_index) & 3))
+        return LADIFF_ERR_SHAPE;
     return diffusion_reverse(reinterpret_cast<Sampler*>(sampler), W, w_split ? &WS : nullptr,
                              ReverseArgs{w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid, coef,
                                          step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
-                                         reuse_time_tables, stream});
+                                         reuse_time_tables, stream, guidance_scales, seeds, prompt_index, draw_init_noise ? 1 : 0});
 }
 
 // ------------------------------------------------------------------ LA-VAE encoder

@@ -12,7 +12,7 @@
 namespace ladiff {
 
 struct GraphKey {
-    static constexpr int CAPACITY = 32;                  // entries; the sampler's key has 26, the decode graph's 20.  One too many aborts.
+    static constexpr int CAPACITY = 32;                  // entries; the sampler's key has 30, the decode graph's 20.  One too many aborts.
     uint64_t v[CAPACITY] = {0};
     int n = 0;
 
@@ -64,6 +64,11 @@ struct ReverseArgs {
     size_t ws_bytes;
     int reuse_time_tables;
     void* stream;
+    // ladiff_diffusion_reverse_prompts: what varies per prompt is device data ([B] arrays, null = the scalar of the call)
+    const float* guidance_scales;
+    const uint64_t* seeds;
+    const uint32_t* prompt_index;
+    int draw_init_noise;                  // the prologue draws the initial noise from `seeds` (schedule position -1) instead of reading init_noise
 };
 
 // Key of a sampler's graphs (prologue graph + step graph, or prologue graph + the pipeline's stage table).  n_params: pointers per weight
@@ -72,6 +77,8 @@ struct ReverseArgs {
 // them as launch arguments instead (nothing captured holds them), so a pipeline call keys four zeros: the loop owner draws a fresh seed per
 // call and must not capture again for it.  The zeros cannot make a pipeline key equal a launch-per-stage key with the generator off:
 // the `pipeline` and `plan_mr` entries (1 and 1 | 2 against 0 and 0) differ between any two such keys.
+// The per-prompt arrays (guidance_scales, seeds, prompt_index) are keyed by POINTER: the prologue graph and the step graphs' tail nodes
+// hold the pointers, the values are read when a graph runs - new scales or seeds in the same buffers replay what is there.
 inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, int plan_mr, int plan_nb, const unsigned noise[4]) {
     GraphKey k;
     k.add(a.ws);
@@ -97,6 +104,10 @@ inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, i
     for (int i = 0; i < 4; ++i) k.add(pipeline ? 0u : noise[i]);
     k.add(weights_hash(a.w, a.w_split, n_params));
     k.add(a.weights_generation);
+    k.add(a.guidance_scales);
+    k.add(a.seeds);
+    k.add(a.prompt_index);
+    k.add(a.draw_init_noise);
     return k;
 }
 

@@ -52,12 +52,14 @@ int launch_zero_fill(float* x, size_t n, hipStream_t s);          // kernel, not
 int launch_silu(const float* x, float* y, size_t n, hipStream_t s);
 int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s);
 int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s);
+                    float g, int cfg, int B, int T, hipStream_t s, const float* gs = nullptr, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0});
 int launch_advance(int32_t* d_step, hipStream_t s);
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
-                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0});
+                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
+                     const float* gs = nullptr);          // gs: [B] per-prompt guidance scales (device) instead of g
 int launch_noise_fill(const NoiseGen& gen, int step0, int n, int B, int T, float* out, hipStream_t s);
 int launch_init_latents(const float* noise, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);
+int launch_init_latents_gen(const NoiseGen& gen, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);   // gen.seeds set
 int launch_finalize_latents(const float* lat, const int32_t* counts, float* z, int B, int T, hipStream_t s, const unsigned* status = nullptr);
 
 int launch_dec_qkv_attn(const float* xs, const float* w, const float* bias, const int32_t* lengths, const int32_t* row_off, float* out,

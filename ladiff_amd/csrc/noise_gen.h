@@ -6,6 +6,9 @@
 // loop, ladiff_noise_fill) computes it where it needs it.
 //   bits:    Philox4x32-10 (Salmon et al., SC'11; the Random123 known-answer vectors are pinned in tests/test_noise.py)
 //            counter = (latent * 64 + column / 4, global prompt, schedule position, 0), key = (seed low, seed high)
+//   per prompt: with `seeds` set, prompt b of the launch has a key of its own, seeds[b], and counter word 1 = index[b] (0 without
+//            `index`): a request's noise is then a function of its (seed, index) alone, whatever batch it sits in and wherever in it.
+//   initial noise: the same function at schedule position -1 (counter word 2 = 0xFFFFFFFF), which no schedule reaches.
 //   normals: Box-Muller on (x0, x1) and (x2, x3): u = ((x >> 9) + 0.5) 2^-23 in (0, 1) - exact in fp32 -,
 //            r = sqrt(-2 ln u_a), (r cos 2 pi u_b, r sin 2 pi u_b) -> columns c, c + 1 (and c + 2, c + 3)
 // oracle/ladiff_oracle.py:device_noise is the numpy restatement (same integers; ln / cos / sin differ by the libraries' last bits).
@@ -19,7 +22,11 @@ struct NoiseGen {              // by value in kernel arguments; on == 0: the cal
     unsigned seed_lo, seed_hi;
     unsigned prompt0;          // global index of this launch's prompt 0
     int on;
+    const unsigned long long* seeds = nullptr;      // [B] device, or null: one key per prompt of the launch instead of `seed`
+    const unsigned* index = nullptr;                // [B] device, or null: counter word 1 of each prompt (with `seeds` only)
 };
+
+constexpr int NOISE_INIT_POSITION = -1;      // schedule position of the initial noise: counter word 2 = 0xFFFFFFFF
 
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned (&out)[4]) {
 #pragma unroll
@@ -34,6 +41,19 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
 }
 
 __device__ __forceinline__ float noise_unit(unsigned x) { return ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f; }   // 2^-23
+
+// Key and prompt word of LOCAL prompt b of a launch: the call's seed and the global index prompt0 + b, or the prompt's own pair.
+// The returned generator is what noise_normal4 takes for that prompt; the branch is uniform over the launch.
+__device__ __forceinline__ NoiseGen noise_of_prompt(const NoiseGen& g, int b, unsigned& prompt) {
+    NoiseGen r = g;
+    prompt = g.prompt0 + (unsigned)b;
+    if (g.seeds != nullptr) {
+        const unsigned long long s = g.seeds[b];
+        r.seed_lo = (unsigned)(s & 0xffffffffull); r.seed_hi = (unsigned)(s >> 32);
+        prompt = g.index != nullptr ? g.index[b] : 0u;
+    }
+    return r;
+}
 
 // the four normals of columns c .. c + 3 (c = 4 * chunk) of latent `t` of global prompt `prompt` at schedule position `step`
 __device__ __forceinline__ void noise_normal4(const NoiseGen& g, int step, unsigned prompt, int t, int chunk, float (&z)[4]) {

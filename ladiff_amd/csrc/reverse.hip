@@ -23,6 +23,11 @@ struct Call {
     int plan_mr, plan_nb;
 };
 
+// the generator of a call with per-prompt seeds: no seed of its own, the arrays by pointer
+NoiseGen prompt_gen(const ReverseArgs& a) {
+    return NoiseGen{0u, 0u, 0u, 1, reinterpret_cast<const unsigned long long*>(a.seeds), a.prompt_index};
+}
+
 // (b) The launch sequences.  Hoisted, once per call: time tables for every step, text cache, initial latents, step counter, first
 // network input.  The time tables depend on (weights, schedule) only: a caller that re-runs with both unchanged in the same workspace
 // may keep them (saves ~30 small GEMM launches per call).  The rest (~50 small launches) depends on this call's text and noise; with a
@@ -32,7 +37,9 @@ int prologue(const Call& c, hipStream_t st) {
     const ReverseWs& r = c.r;
     if (a.n_text > 1) LADIFF_TRY(denoiser_text_cache(c.W, a.text_emb, c.B2, r.tables, a.n_steps, r.cache, r.fwd, r.fwd_floats, st, a.n_text));
     else LADIFF_TRY(denoiser_text_static(c.W, a.text_emb, c.B2, r.cache, r.fwd, r.fwd_floats, st));      // the c table: per window, below
-    LADIFF_TRY(launch_init_latents(a.init_noise, a.counts, a.init_noise_sigma, r.latents, a.B, a.T, st));
+    if (a.draw_init_noise && a.init_noise == nullptr)      // a tensor still wins over the generator
+        LADIFF_TRY(launch_init_latents_gen(prompt_gen(a), a.counts, a.init_noise_sigma, r.latents, a.B, a.T, st));
+    else LADIFF_TRY(launch_init_latents(a.init_noise, a.counts, a.init_noise_sigma, r.latents, a.B, a.T, st));
     // [0] step index, [1] tail-kernel ticket, [2] window base.  A KERNEL, not hipMemsetAsync: this runs inside the captured prologue
     // graph, and a memset NODE is what an older exec replayed wrongly (see g_graph_epoch)
     LADIFF_TRY(launch_zero_fill(reinterpret_cast<float*>(r.d_step), 4, st));
@@ -48,7 +55,7 @@ int one_step(const Call& c, hipStream_t st) {
     LADIFF_TRY(denoiser_forward(c.W, c.WSp, r.tables, r.d_step, r.cache, r.window, r.latents, a.B, c.dup, a.T, a.counts, r.eps, r.fwd,
                                 r.fwd_floats, st, 0, c.B2, 1, a.n_text, r.d_step + 2));
     return launch_step_tail(c.xio, c.xios, c.W.norm.g, c.W.norm.b, r.latents, a.coef, r.d_step, a.step_noise, c.W.query_pe,
-                            a.guidance_scale, a.cfg, a.B, a.T, st, c.gen);
+                            a.guidance_scale, a.cfg, a.B, a.T, st, c.gen, a.guidance_scales);
 }
 
 // c-table rows of the window that starts at step `lo` (plain launches, outside the graphs: `lo` changes per window)
@@ -133,7 +140,7 @@ int run_windows(Sampler* sp, const Call& c) {
         if (c.pipeline) {
             LADIFF_TRY(launch_systolic_loop(c.W, r.sys, r.tables, den_cache_tkv(r.cache, c.B2, 1), den_cache_ctab(r.cache, c.B2, 1), r.window,
                                             a.coef, a.step_noise, r.latents, a.counts, a.guidance_scale, a.B, a.T, lo, r.window, c.WSp ? 0 : 1,
-                                            c.plan_mr, c.plan_nb, c.s, a.cfg, sp->fault_wg, sp->timeout_ticks, c.gen));
+                                            c.plan_mr, c.plan_nb, c.s, a.cfg, sp->fault_wg, sp->timeout_ticks, c.gen, a.guidance_scales));
         } else {
             for (int i = 0; i < r.window / sp->unroll; ++i) LADIFF_HIP(hipGraphLaunch(sp->exec, c.s));
         }
@@ -154,6 +161,9 @@ int diffusion_reverse(Sampler* sp, const DenoiserW& W, const DenoiserW* WSp, con
     // A generator that is off is all zeros: its seed must not be part of any graph key (the Python loop owner draws a fresh seed per call,
     // also for deterministic schedules - a key that changed with it re-captured ~150-node graphs on every launch-per-stage call).
     if (sp != nullptr && a.step_noise == nullptr && sp->gen.on) c.gen = sp->gen;
+    // per-prompt seeds need no handle to carry them (they are arguments of the call) and replace the sampler's seed: the words that
+    // enter the key are then constants, the arrays are keyed by pointer
+    if (a.seeds != nullptr && a.step_noise == nullptr) c.gen = prompt_gen(a);
     den_loop_io(c.r.fwd, c.B2 * a.T, &c.xio, &c.xios);
     if (WSp == nullptr) c.xios = nullptr;
     // without guidance the pipeline runs one-branch 16-row blocks, which need the latent counts on the host (or no masking at all)

@@ -560,10 +560,13 @@ int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s) {
 // Classifier-free guidance + one scheduler step (ladiff.py:487-492), elementwise on [B,T,256].
 __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ lat,
                                                        const float* __restrict__ coef, const int32_t* __restrict__ d_step,
-                                                       const float* __restrict__ noise, float g, int cfg, size_t n4) {
+                                                       const float* __restrict__ noise, float g, const float* __restrict__ gs,
+                                                       int cfg, int T, size_t n4, const NoiseGen gen) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
     const int step = *d_step;
+    const int row = (int)(i / (D / 4));                                  // row = b * T + t
+    if (gs != nullptr) g = gs[row / T];                                  // the prompt's own scale (launch-uniform branch)
     const float* c = coef + (size_t)step * LADIFF_COEF_STRIDE;
     const float sa = c[0], sb = c[1], kx0 = c[2], kx = c[3], ke = c[4], kn = c[5];
     f32x4 e = ld4(eps + i * 4);
@@ -574,7 +577,13 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     }
     f32x4 x = ld4(lat + i * 4);
     f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    if (noise != nullptr && kn != 0.f) z = ld4(noise + ((size_t)step * n4 + i) * 4);
+    if (gen.on && kn != 0.f) {
+        float zz[4];
+        unsigned prompt;
+        const NoiseGen pg = noise_of_prompt(gen, row / T, prompt);
+        noise_normal4(pg, step, prompt, row % T, (int)(i % (D / 4)), zz);
+        z = f32x4{zz[0], zz[1], zz[2], zz[3]};
+    } else if (noise != nullptr && kn != 0.f) z = ld4(noise + ((size_t)step * n4 + i) * 4);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float x0 = (x[k] - sb * e[k]) / sa;
@@ -583,9 +592,10 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     st4(lat + i * 4, x);
 }
 int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s) {
+                    float g, int cfg, int B, int T, hipStream_t s, const float* gs, const NoiseGen& gen) {
     const size_t n4 = (size_t)B * T * D / 4;
-    hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, coef, d_step, noise, g, cfg, n4);
+    hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, coef, d_step, noise, g, gs, cfg, T, n4,
+                       gen);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }
@@ -600,7 +610,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
                                                         const float* __restrict__ nb, float* __restrict__ lat,
                                                         const float* __restrict__ coef, int32_t* __restrict__ d_step,
                                                         const float* __restrict__ noise, const float* __restrict__ pe, float g,
-                                                        int cfg, int B, int T, const NoiseGen gen) {
+                                                        const float* __restrict__ gs, int cfg, int B, int T, const NoiseGen gen) {
     const int step = d_step[0];
     const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);      // row = b * T + t of the B prompts
     const int c = (threadIdx.x & 63) * 4;
@@ -608,6 +618,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
     if (row < M) {
         const float* cf = coef + (size_t)step * LADIFF_COEF_STRIDE;
         const float sa = cf[0], sb = cf[1], kx0 = cf[2], kx = cf[3], ke = cf[4], kn = cf[5];
+        if (gs != nullptr) g = gs[row / T];                                // the prompt's own scale (launch-uniform branch)
         const f32x4 gg = ld4(ng + c), bb = ld4(nb + c);
         f32x4 eu = ld4(x + (size_t)row * D + c), ec = eu;
         if (cfg) ec = ld4(x + (size_t)(M + row) * D + c);
@@ -624,7 +635,9 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
         f32x4 z = {0.f, 0.f, 0.f, 0.f};
         if (gen.on && kn != 0.f) {       // drawn here (noise_gen.h): the same function of (seed, step, global prompt, latent, column) as everywhere
             float zz[4];
-            noise_normal4(gen, step, gen.prompt0 + (unsigned)(row / T), row % T, c / 4, zz);
+            unsigned prompt;
+            const NoiseGen pg = noise_of_prompt(gen, row / T, prompt);
+            noise_normal4(pg, step, prompt, row % T, c / 4, zz);
             z = f32x4{zz[0], zz[1], zz[2], zz[3]};
         } else if (noise != nullptr && kn != 0.f) z = ld4(noise + ((size_t)step * M + row) * D + c);
         const f32x4 p = ld4(pe + (size_t)(row % T) * D + c);
@@ -651,15 +664,16 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
     }
 }
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
-                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen) {
+                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs) {
     const int M = B * T;
     hipLaunchKernelGGL(step_tail_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, x, xs, ng, nb, lat, coef,
-                       d_step, noise, pe, g, cfg, B, T, gen);
+                       d_step, noise, pe, g, gs, cfg, B, T, gen);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }
 
 // the generator's values as a tensor: out[i][b][t][:] = the noise of schedule position step0 + i, global prompt prompt0 + b, latent t
+// (with gen.seeds: of the prompt with key seeds[b] and index[b]); step0 = -1 starts at the initial noise
 __global__ __launch_bounds__(256) void noise_fill_kernel(const NoiseGen gen, int step0, int n, int B, int T, float* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;          // one 16-byte chunk per thread
     const size_t per_step = (size_t)B * T * (D / 4);
@@ -668,7 +682,9 @@ __global__ __launch_bounds__(256) void noise_fill_kernel(const NoiseGen gen, int
     const size_t r = i % per_step;
     const int chunk = (int)(r % (D / 4)), row = (int)(r / (D / 4));
     float z[4];
-    noise_normal4(gen, step0 + st, gen.prompt0 + (unsigned)(row / T), row % T, chunk, z);
+    unsigned prompt;
+    const NoiseGen pg = noise_of_prompt(gen, row / T, prompt);
+    noise_normal4(pg, step0 + st, prompt, row % T, chunk, z);
     st4(out + i * 4, f32x4{z[0], z[1], z[2], z[3]});
 }
 int launch_noise_fill(const NoiseGen& gen, int step0, int n, int B, int T, float* out, hipStream_t s) {
@@ -702,6 +718,32 @@ __global__ __launch_bounds__(256) void init_latents_kernel(const float* __restri
 int launch_init_latents(const float* noise, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s) {
     const int M = B * T;
     hipLaunchKernelGGL(init_latents_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, noise, counts, sigma, T, M, lat);
+    LADIFF_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same with the noise drawn here: latents[b,t] = sigma * valid * normal(seed_b, index_b, position -1, t, column) (noise_gen.h) - no
+// [B,T,256] noise tensor is read.  gen.seeds is set (the caller checks).
+__global__ __launch_bounds__(256) void init_latents_gen_kernel(const NoiseGen gen, const int32_t* __restrict__ counts, float sigma, int T,
+                                                               int M, float* __restrict__ lat) {
+    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int c = (threadIdx.x & 63) * 4;
+    if (row >= M) return;
+    const int b = row / T, t = row % T;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (counts == nullptr || t < counts[b]) {
+        float z[4];
+        unsigned prompt;
+        const NoiseGen pg = noise_of_prompt(gen, b, prompt);
+        noise_normal4(pg, NOISE_INIT_POSITION, prompt, t, c / 4, z);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = z[i] * sigma;
+    }
+    st4(lat + (size_t)row * D + c, v);
+}
+int launch_init_latents_gen(const NoiseGen& gen, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s) {
+    const int M = B * T;
+    hipLaunchKernelGGL(init_latents_gen_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, gen, counts, sigma, T, M, lat);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }

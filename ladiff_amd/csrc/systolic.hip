@@ -108,6 +108,7 @@ struct SysArgs {
     float* lat;                           // latents [B][T][256]
     const int32_t* counts;
     float gscale;
+    const float* gscales;                 // [B] or null: the guidance scale of each prompt instead of gscale
     int B, B2, T, P, NB, step_lo, n_steps, n_ctab;          // B2 = sample-branches: 2 B with guidance (uncond | cond), B without
     int force_mismatch;                   // test aid: one workgroup reports a placement that disagrees (ladiff_debug_set_xcd_local(2))
     int split;                            // 1: a block holds ONE guidance branch of its P prompts (block 2g + br), 0: both
@@ -1914,7 +1915,7 @@ template <int MR, int WS, int HO>
 struct TailRole {
     static constexpr int RT = 16 * MR, NW = 4 * WS, NQ = 16 / NW;        // (prompt, latent) pairs per wave: <= 16 per unit
     struct Geo { int lat[NQ], t[NQ], rc[NQ], pad[NQ]; };                // latent row, position, conditional-branch row of pair q; padding row of a slot without a pair
-    struct Pay { f32x4 eu[NQ], ec[NQ], lt[NQ], zz[NQ], pe[NQ]; };
+    struct Pay { f32x4 eu[NQ], ec[NQ], lt[NQ], zz[NQ], pe[NQ]; float gs[NQ]; };     // gs: the guidance scale of the pair's own prompt
     const SysArgs& p; const Stage& st;
     f32x4 gg, bb;
     __amdgpu_buffer_rsrc_t rin, rout;
@@ -1989,9 +1990,15 @@ struct TailRole {
                 y.ec[i] = ld_sc1(rin, bc + g.rc[i] * 1024 + c * 4);
                 y.lt[i] = ld4(p.lat + (size_t)g.lat[i] * D + c);
                 y.pe[i] = ld4(p.pe + (size_t)g.t[i] * D + c);
+                // the pair's prompt of this launch, g.lat / T, selects its scale and its noise key; both branches are uniform over the
+                // launch, and a launch without the arrays divides nowhere it did not before
+                y.gs[i] = p.gscale;
+                if (p.gscales != nullptr) y.gs[i] = p.gscales[g.lat[i] / T];
                 if (p.gen.on && kn != 0.f) {
                     float zz[4];
-                    noise_normal4(p.gen, step, p.gen.prompt0 + (unsigned)(g.lat[i] / T), g.t[i], lane, zz);
+                    unsigned prompt;
+                    const NoiseGen pg = noise_of_prompt(p.gen, g.lat[i] / T, prompt);
+                    noise_normal4(pg, step, prompt, g.t[i], lane, zz);
                     y.zz[i] = f32x4{zz[0], zz[1], zz[2], zz[3]};
                 } else if (p.noise != nullptr && kn != 0.f) y.zz[i] = ld4(p.noise + ((size_t)step * p.B * T + g.lat[i]) * D + c);
             } else if (HO) {                                             // the tickets of a slot that only pads (Red2Role::issue)
@@ -2019,7 +2026,7 @@ struct TailRole {
                 for (int k = 0; k < 4; ++k) ec[k] = (ec[k] - mean) * rstd * gg[k] + bb[k];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float e = eu[k] + p.gscale * (ec[k] - eu[k]);
+                    const float e = eu[k] + y.gs[i] * (ec[k] - eu[k]);
                     const float x0 = (l[k] - sb * e) / sa;
                     l[k] = kx0 * x0 + kx * l[k] + ke * e + kn * y.zz[i][k];
                     xn[k] = l[k] + y.pe[i][k];
@@ -2335,7 +2342,7 @@ int sys_reset_status(float* ws, hipStream_t s) {
 int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab,
                          const float* coef, const float* noise, float* lat, const int32_t* counts, float gscale, int B, int T,
                          int step_lo, int n, int fp32, int MR, int NB, hipStream_t s, int cfg, int fault_wg, unsigned long long timeout_ticks,
-                         const NoiseGen& gen) {
+                         const NoiseGen& gen, const float* gscales) {
     // fault_wg / timeout_ticks: the caller's SAMPLER's fault injection (ladiff_sampler_set_fault; -1 / 0 = none / default bound)
     const SysLayout L = sys_layout(MR, NB);
     SysArgs a;
@@ -2344,7 +2351,7 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     a.flags = reinterpret_cast<unsigned*>(ws + L.off_flags);
     a.status = reinterpret_cast<unsigned*>(ws + L.off_status);
     a.tables = tables; a.tkv = tkv; a.ctab = ctab; a.coef = coef; a.noise = noise; a.pe = W.query_pe; a.ng = W.norm.g; a.nb = W.norm.b;
-    a.lat = lat; a.counts = counts; a.gscale = gscale; a.B = B; a.B2 = cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
+    a.lat = lat; a.counts = counts; a.gscale = gscale; a.gscales = gscales; a.B = B; a.B2 = cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
     a.n_ctab = n_ctab;
     a.split = cfg ? L.split : 0;       // no guidance: every block is a unit of its own (sys_pack_blocks)
     a.force_mismatch = g_xcd_local == 2 ? 1 : 0;

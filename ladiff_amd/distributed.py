@@ -45,6 +45,14 @@ def shard_prompts(text_emb, lengths, init_noise, rank, world):
     return text, list(lengths[lo:hi]), noise, (lo, hi)
 
 
+def shard_prompt_params(span, **arrays):
+    """Slice per-prompt arrays of the GLOBAL batch (guidance_scale=, seeds=, prompt_index= of `LADIFF.sample`) by the (lo, hi) that
+    `shard_prompts` returned.  None and plain numbers pass through.  A prompt keeps its own (seed, index) on whatever rank it lands, so
+    its motion does not depend on the world size."""
+    lo, hi = span
+    return {k: (v if v is None or not (torch.is_tensor(v) and v.dim() > 0 or hasattr(v, "__len__")) else v[lo:hi]) for k, v in arrays.items()}
+
+
 _PAD_CACHE = {}
 
 

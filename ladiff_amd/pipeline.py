@@ -308,6 +308,10 @@ class LADIFF(nn.Module):
             "text": torch.empty(2 * B, n_text, 768, dtype=torch.float32, device=dev), "n_text": n_text,
             "noise": torch.empty(B, T, 256, dtype=torch.float32, device=dev),
             "counts": torch.empty(B, dtype=torch.int32, device=dev),
+            # per-prompt guidance scales, noise keys and noise indices: the loop takes them by pointer (graphs key the pointer, not the values)
+            "gscales": torch.empty(B, dtype=torch.float32, device=dev),
+            "seeds": torch.empty(B, dtype=torch.int64, device=dev),
+            "pindex": torch.empty(B, dtype=torch.int32, device=dev),
             # per-step noise (DDPM / eta > 0): the CALLER's tensor is used in place when it is a contiguous fp32 tensor on this device
             # (1000 steps x 128 prompts are 655 MB: not held twice, not copied per call); otherwise a plan-owned copy, made on first need
             "step_noise": None,
@@ -387,12 +391,63 @@ class LADIFF(nn.Module):
             lo = hi
         return spans
 
-    def _diffusion_reverse(self, encoder_hidden_states, lengths=None, init_noise=None, step_noise=None, noise_seed=None):
+    @staticmethod
+    def _per_prompt(values, B, name, kind):
+        """A caller's per-prompt sequence or tensor as a [B] tensor of the dtype the loop reads (kind "f": float32; "u64" / "u32":
+        unsigned values carried in int64 / int32 words).  None stays None."""
+        if values is None:
+            return None
+        if torch.is_tensor(values):
+            t = values.detach()
+            t = t.to(torch.float32) if kind == "f" else (t.to(torch.int64) if kind == "u64" else t.to(torch.int64).bitwise_and(0xFFFFFFFF))
+        elif kind == "f":
+            t = torch.tensor([float(v) for v in values], dtype=torch.float32)
+        else:
+            mask = (1 << 64) - 1 if kind == "u64" else 0xFFFFFFFF
+            ints = [int(v) & mask for v in values]
+            t = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in ints], dtype=torch.int64)
+        if kind == "u32":                                     # 0 .. 2^32 - 1 held in int64: the low word's bits as int32
+            t = torch.where(t >= (1 << 31), t - (1 << 32), t).to(torch.int32)
+        if t.dim() != 1 or t.numel() != B:
+            raise ValueError(f"{name}: {tuple(t.shape)} values for {B} prompts")
+        return t
+
+    def _prompt_params(self, B, guidance_scale, seeds, prompt_index):
+        """The per-prompt arguments of a call, checked: {"gscales", "seeds", "pindex": [B] tensors or None, "scalar_g": a number given
+        in place of `self.guidance_scale`, or None}."""
+        scalar_g = None
+        if torch.is_tensor(guidance_scale) and guidance_scale.dim() == 0:
+            guidance_scale = float(guidance_scale)
+        if guidance_scale is not None and not torch.is_tensor(guidance_scale) and not hasattr(guidance_scale, "__len__"):
+            scalar_g, guidance_scale = float(guidance_scale), None
+        if prompt_index is not None and seeds is None:
+            raise ValueError("prompt_index needs seeds")
+        per = {"gscales": self._per_prompt(guidance_scale, B, "guidance_scale", "f"), "seeds": self._per_prompt(seeds, B, "seeds", "u64"),
+               "pindex": self._per_prompt(prompt_index, B, "prompt_index", "u32"), "scalar_g": scalar_g}
+        if per["gscales"] is not None and not self.do_classifier_free_guidance:
+            raise ValueError("per-prompt guidance scales need a model built with classifier-free guidance (guidance_scale > 1)")
+        return per
+
+    def _diffusion_reverse(self, encoder_hidden_states, lengths=None, init_noise=None, step_noise=None, noise_seed=None, *,
+                           guidance_scale=None, seeds=None, prompt_index=None):
         """text_emb [2B,1,768] (unconditional half first), lengths list[int] -> z [max_it, B, 256]  (ladiff.py:333-571).
         Stochastic schedules (DDPM, eta > 0): `step_noise` [n,B,T,256] if given; otherwise the noise is drawn on the device where it
         is consumed (csrc/noise_gen.h) from `noise_seed` (default: a seed taken from torch's CPU generator, so torch.manual_seed makes
-        a run reproducible) - the reference draws it inside scheduler.step, ladiff.py:492.  `last_noise_seed` holds the seed used."""
+        a run reproducible) - the reference draws it inside scheduler.step, ladiff.py:492.  `last_noise_seed` holds the seed used.
+
+        The prompts of one batch as separate requests (each argument a sequence or tensor of B values):
+        `guidance_scale`: the scale of each prompt (a plain number replaces `self.guidance_scale` for this call).  Needs a model built
+          with classifier-free guidance.  A per-prompt value <= 1 is simply evaluated, eps_u + g (eps_c - eps_u): 1.0 gives the
+          conditional prediction, it does not switch the unconditional branch off.
+        `seeds`, `prompt_index`: prompt b draws its noise with key seeds[b] and index prompt_index[b] (0 without `prompt_index`) instead
+          of (`noise_seed`, `noise_first_prompt` + b) - the same (seed, index) gives the same motion whatever the rest of the batch is,
+          however it is chunked or sharded.  With `seeds` and no `init_noise` the initial noise is drawn on the device too (schedule
+          position -1 of the same generator) and torch's generators are not touched.
+        The values travel in per-plan device buffers: new values do not capture the graphs again."""
         dev = encoder_hidden_states.device
+        per = {}
+        if guidance_scale is not None or seeds is not None or prompt_index is not None:
+            per = self._prompt_params(len(lengths), guidance_scale, seeds, prompt_index)     # argument errors first: host work only
         if not encoder_hidden_states.is_cuda:
             raise _lib.LadiffHipError("_diffusion_reverse needs GPU tensors; there is no CPU fallback")
         self._check_loaded_weights()
@@ -412,24 +467,26 @@ class LADIFF(nn.Module):
         T = counts[0] if self.test_efficiency else self.max_it     # ladiff.py:381
         self._last = []
         spans = self._chunks(B)
-        if step_noise is None and noise_seed is None:
+        if step_noise is None and noise_seed is None and seeds is None:
             noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.last_noise_seed = None if step_noise is not None else int(noise_seed)
+        self.last_noise_seed = None if step_noise is not None or noise_seed is None else int(noise_seed)
         first = int(self.noise_first_prompt)
         if len(spans) == 1:
-            return self._reverse_one(encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed, first)
+            return self._reverse_one(encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed, first, per)
         # prompts are independent (attention is per sample, guidance pairs the two branches of one prompt): a large batch is
         # several launches of the loop on contiguous prompt ranges, the noise drawn for the whole batch and sliced
-        if init_noise is None:
+        if init_noise is None and seeds is None:
             init_noise = torch.randn(B, T, 256, device=dev, dtype=torch.float32)       # ladiff.py:380-385
         text = encoder_hidden_states.reshape(dup, B, n_text, 768)
         zs = []
         for lo, hi in spans:
+            part = {k: (v[lo:hi] if torch.is_tensor(v) else v) for k, v in per.items()}      # a caller's prompt_index is not shifted
             zs.append(self._reverse_one(text[:, lo:hi].reshape(dup * (hi - lo), n_text, 768), lengths[lo:hi], counts[lo:hi], T,
-                                        init_noise[lo:hi], None if step_noise is None else step_noise[:, lo:hi], noise_seed, first + lo))
+                                        None if init_noise is None else init_noise[lo:hi],
+                                        None if step_noise is None else step_noise[:, lo:hi], noise_seed, first + lo, part))
         return torch.cat(zs, dim=1)
 
-    def _reverse_one(self, encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed=None, first_prompt=0):
+    def _reverse_one(self, encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed=None, first_prompt=0, per=None):
         """One launch sequence of the loop on B prompts: prologue graph, N steps (pipeline kernel or step graphs), final masking."""
         L = _lib.lib()
         dev = encoder_hidden_states.device
@@ -444,10 +501,13 @@ class LADIFF(nn.Module):
         sampler = plan["sampler"]
         if self._stream is None or self._stream.device != dev:
             self._stream = torch.cuda.Stream(device=dev)
-        if init_noise is None:
+        per = per or {}
+        gscales, seeds, pindex = per.get("gscales"), per.get("seeds"), per.get("pindex")
+        draw_init = init_noise is None and seeds is not None       # drawn in the prologue from the prompts' own keys: no randn, no tensor
+        if init_noise is None and not draw_init:
             init_noise = torch.randn(B, T, 256, device=dev, dtype=torch.float32)       # ladiff.py:380-385
         generated = need_noise and step_noise is None      # drawn inside the loop, keyed by (seed, step, global prompt, latent, column)
-        if generated and sampler is None:
+        if generated and sampler is None and seeds is None:
             # no sampler handle to carry the seed (use_graph=False): the same values as a tensor (n x B x T x 256 floats)
             step_noise = self.noise_tensor(noise_seed, n, B, T, first_prompt=first_prompt, device=dev)
             generated = False
@@ -476,17 +536,19 @@ class LADIFF(nn.Module):
         def enqueue(loop):
             if sampler is not None:
                 _lib.check(L.ladiff_sampler_set_loop(sampler, loop_codes[loop]))
-            _lib.check(L.ladiff_diffusion_reverse(
+            _lib.check(L.ladiff_diffusion_reverse_prompts(
                 sampler, wt.array,
                 wt.split_array() if _lib.is_split(self.precision) else None, wt.generation, _lib.ptr(plan["text"]),
-                _lib.ptr(plan["noise"]),
+                None if draw_init else _lib.ptr(plan["noise"]),
                 # TEST_EFFICIENCY: no masks inside the denoiser and no zeroing of the initial noise (ladiff.py:381-390,
                 # ladiff_denoiser.py:254) - but the final zeroing of ladiff.py:559-566 has no such switch
                 None if self.test_efficiency else plan["counts"].data_ptr(), plan["counts"].data_ptr(),
                 None if self.test_efficiency else (ctypes.c_int32 * B)(*counts),       # host copy: length-aware block packing
                 _lib.ptr(plan["sinus"]), _lib.ptr(plan["coef"]), _lib.ptr(noise_t) if noise_t is not None else None,
-                self.guidance_scale, float(sch.init_noise_sigma), 1 if cfg else 0, B, T, n_text, n, _lib.ptr(plan["z"]),
-                _lib.ptr(plan["ws"]), plan["ws_bytes"], 1 if plan["tables_key"] == wt.key else 0, run.cuda_stream))
+                self.guidance_scale if per.get("scalar_g") is None else per["scalar_g"], float(sch.init_noise_sigma), 1 if cfg else 0, B, T,
+                n_text, n, _lib.ptr(plan["z"]), _lib.ptr(plan["ws"]), plan["ws_bytes"], 1 if plan["tables_key"] == wt.key else 0,
+                None if gscales is None else _lib.ptr(plan["gscales"]), None if seeds is None else plan["seeds"].data_ptr(),
+                None if pindex is None else plan["pindex"].data_ptr(), 1 if draw_init else 0, run.cuda_stream))
             plan["tables_key"] = wt.key
             # the loop's status words follow it on the stream into pinned memory: 8 bytes, no host synchronisation here
             slot = plan["launches"] % 8
@@ -500,7 +562,11 @@ class LADIFF(nn.Module):
 
         with torch.cuda.stream(run):
             plan["text"][:dup * B].copy_(encoder_hidden_states.reshape(dup * B, n_text, 768))
-            plan["noise"].copy_(init_noise)
+            if not draw_init:
+                plan["noise"].copy_(init_noise)
+            for name, values in (("gscales", gscales), ("seeds", seeds), ("pindex", pindex)):
+                if values is not None:
+                    plan[name].copy_(values, non_blocking=True)
             plan["counts"].copy_(_lib.device_ints(counts, dev))       # device-to-device: the graph bakes plan["counts"] in
             if noise_t is not None and noise_t is not step_noise:
                 noise_t.copy_(step_noise)
@@ -517,10 +583,22 @@ class LADIFF(nn.Module):
         return plan["z"].clone()
 
     @staticmethod
-    def noise_tensor(seed, n_steps, B, T, first_prompt=0, first_step=0, device="cuda:0"):
+    def noise_tensor(seed, n_steps, B, T, first_prompt=0, first_step=0, device="cuda:0", seeds=None, prompt_index=None):
         """The device generator's values as a tensor [n_steps,B,T,256] (what a call with noise_seed=seed consumes at schedule
-        positions first_step .. for global prompts first_prompt ..): for tests and for callers that want to keep the noise."""
+        positions first_step .. for global prompts first_prompt ..): for tests and for callers that want to keep the noise.
+        With `seeds` (and optionally `prompt_index`), B values each: what a call with those per-prompt keys consumes (`seed` and
+        `first_prompt` are then not used); first_step=-1 starts at the initial noise."""
         out = torch.empty(n_steps, B, T, 256, dtype=torch.float32, device=device)
+        if seeds is not None:
+            sd = LADIFF._per_prompt(seeds, B, "seeds", "u64").to(out.device)
+            ix = LADIFF._per_prompt(prompt_index, B, "prompt_index", "u32")
+            ix = None if ix is None else ix.to(out.device)
+            with torch.cuda.device(out.device):
+                _lib.check(_lib.lib().ladiff_noise_fill_prompts(sd.data_ptr(), None if ix is None else ix.data_ptr(), int(first_step), int(n_steps),
+                                                                int(B), int(T), _lib.ptr(out), torch.cuda.current_stream(out.device).cuda_stream))
+            return out
+        if prompt_index is not None:
+            raise ValueError("prompt_index needs seeds")
         with torch.cuda.device(out.device):
             _lib.check(_lib.lib().ladiff_noise_fill(int(seed), int(first_prompt), int(first_step), int(n_steps), int(B), int(T),
                                                     _lib.ptr(out), torch.cuda.current_stream(out.device).cuda_stream))
@@ -577,11 +655,14 @@ class LADIFF(nn.Module):
         return code.value, info.value
 
     # ------------------------------------------------------------------ callers' surface
-    def sample(self, text_emb, lengths, init_noise=None, step_noise=None, check=True, noise_seed=None):
+    def sample(self, text_emb, lengths, init_noise=None, step_noise=None, check=True, noise_seed=None, *, guidance_scale=None, seeds=None,
+               prompt_index=None):
         """text embeddings -> (z [max_it,B,256], feats [B,max(len),nfeats]): ladiff.py:266 + :283.  Returns checked frames: the
         decode is queued, then the host waits for the loop's status words (LadiffHipError if the loop was abandoned).
-        check=False skips the wait (the host may then queue a call ahead) - the caller owes a `check()` before using the frames."""
-        z = self._diffusion_reverse(text_emb, lengths, init_noise=init_noise, step_noise=step_noise, noise_seed=noise_seed)
+        check=False skips the wait (the host may then queue a call ahead) - the caller owes a `check()` before using the frames.
+        guidance_scale / seeds / prompt_index: one value per prompt, see `_diffusion_reverse`."""
+        z = self._diffusion_reverse(text_emb, lengths, init_noise=init_noise, step_noise=step_noise, noise_seed=noise_seed,
+                                    guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index)
         feats = self.vae.decode(z, lengths)
         if check:
             self.check()
@@ -600,7 +681,10 @@ class LADIFF(nn.Module):
                 z, _, _ = self.vae.encode(batch["motion"].detach().to(self.device), lengths)
         else:
             text_emb = self.text_encoder(self._guided_texts(texts))
-            z = self._diffusion_reverse(text_emb, lengths)
+            # optional per-prompt requests of the batch: "guidance_scale" (B values or one number) and "seed" (B noise keys);
+            # a batch without them makes the call it always made
+            per = {kw: batch[key] for key, kw in (("guidance_scale", "guidance_scale"), ("seed", "seeds")) if batch.get(key) is not None}
+            z = self._diffusion_reverse(text_emb, lengths, **per)
         with torch.no_grad():
             if latentwise_gen:                                      # ladiff.py:274-283
                 lengths = list(lengths) * self.max_it
