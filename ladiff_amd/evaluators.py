@@ -119,6 +119,8 @@ class TextEncoderBiGRUCo(_Frozen):
         p = pos_onehot.detach().to(device=w.device, dtype=torch.float32).contiguous()
         B, T, _ = w.shape
         lens = _lens(cap_lens, B, w.device)
+        if int(lens.max()) > T:
+            raise ValueError("a length exceeds the sequence")
         out = torch.empty(B, 512, dtype=torch.float32, device=w.device)
         wsb = L.ladiff_t2m_text_workspace_bytes(B, T)
         ws = _lib.workspace(wsb, w.device)

@@ -83,6 +83,18 @@ def test_t2m_evaluator_tables_match_checkpoint_keys():
         MotionEncoderBiGRUCo(512, 512, 512)
 
 
+def test_t2m_gru_encoders_refuse_a_length_beyond_the_sequence(lib):
+    """Raised on the host before anything is queued (the kernel would clamp in silence): CPU tensors never reach the library."""
+    from ladiff_amd import MotionEncoderBiGRUCo, TextEncoderBiGRUCo
+    motion, text = MotionEncoderBiGRUCo(512, 1024, 512), TextEncoderBiGRUCo(300, 15, 512, 512)
+    with pytest.raises(ValueError, match="a length exceeds the sequence"):
+        motion(torch.zeros(2, 3, 512), torch.tensor([3, 4]))
+    with pytest.raises(ValueError, match="a length exceeds the sequence"):
+        text(torch.zeros(2, 3, 300), torch.zeros(2, 3, 15), torch.tensor([4, 1]))
+    with pytest.raises(RuntimeError, match="greater than 0"):
+        text(torch.zeros(2, 3, 300), torch.zeros(2, 3, 15), torch.tensor([0, 1]))
+
+
 def test_workspace_queries(lib):
     assert lib.ladiff_denoiser_tables_floats(50) == 50 * 9 * 1536
     assert lib.ladiff_denoiser_text_cache_floats(256, 50, 1) == 256 * 256 + 9 * 256 * 512 + 9 * 256 * 256 + 9 * 50 * 257 * 256

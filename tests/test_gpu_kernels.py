@@ -7,7 +7,7 @@ import torch.nn.functional as F
 
 from ladiff_amd import _lib
 from oracle import ladiff_oracle as orc
-from trained_like import layernorm_row_bound, offset_rows, spread_affine
+from trained_like import bound, layernorm_row_bound, offset_rows, spread_affine
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -44,7 +44,7 @@ def gemm(A, W, bias=None, A2=None, res=None, ln=None, act="none"):
 def ref_gemm(A, W, bias=None, A2=None, res=None, ln=None, act="none"):
     X = A if A2 is None else torch.cat([A, A2], dim=1)
     y = F.linear(X.double(), W.double(), None if bias is None else bias.double())
-    y = {"none": lambda v: v, "relu": F.relu, "gelu": F.gelu, "silu": F.silu}[act](y)
+    y = {"none": lambda v: v, "relu": F.relu, "gelu": F.gelu, "silu": F.silu, "lrelu": lambda v: F.leaky_relu(v, 0.2)}[act](y)
     if res is not None:
         y = y + res.double()
     if ln is not None:
@@ -93,6 +93,59 @@ def test_gemm_shape_errors():
     rc = lib().ladiff_gemm(_lib.ptr(A), 40, None, 0, 40, _lib.ptr(W), 40, None, None, 0, None, None, _lib.ptr(Y), 8,
                            4, 8, 40, 0, _lib.stream_ptr())
     assert rc == -2    # K must be a multiple of 32
+
+
+def gemm_ld(A, W, bias=None, res=None, act="none", lda=None, ldy=None, ldres=None):
+    """`gemm` with leading dimensions of its own: A lives in [M, lda], res in [M, ldres], Y in [M, ldy], every padding column (A past K, res and
+    Y past N) NaN.  Returns Y whole; nothing may be written past column N and nothing read past column K."""
+    (M, K), N = A.shape, W.shape[0]
+    lda, ldy, ldres = lda or K, ldy or N, ldres or N
+    nan = float("nan")
+    A_ = torch.full((M, lda), nan, device=DEV); A_[:, :K] = A.to(DEV)
+    Y = torch.full((M, ldy), nan, device=DEV)
+    r_ = None
+    if res is not None:
+        r_ = torch.full((M, ldres), nan, device=DEV); r_[:, :N] = res.to(DEV)
+    W_, b_ = W.to(DEV).contiguous(), None if bias is None else bias.to(DEV).contiguous()
+    _lib.check(lib().ladiff_gemm(_lib.ptr(A_), lda, None, 0, K, _lib.ptr(W_), K, _lib.ptr(b_), _lib.ptr(r_), ldres if res is not None else 0,
+                                 None, None, _lib.ptr(Y), ldy, M, N, K, _lib.ACT[act], _lib.stream_ptr()))
+    sync()
+    Y = Y.cpu()
+    assert torch.isnan(Y[:, N:]).all(), "columns past N were written"
+    assert torch.isfinite(Y[:, :N]).all(), "a padding column was read"
+    return Y
+
+
+# exactly the operand geometries csrc/evaluator.hip issues, on both sides of M = 4096 (from there on N % 128 == 0 goes to gemm_big.hip, N = 300
+# to the 128 x 128 staged tile):  (M, N, K, act, residual with lda = K, ldy = ldres = 320)
+EVALUATOR_GEOMETRIES = (
+    [(M, 512, 1056, "lrelu", False) for M in (4116, 4095)] +        # conv0 at nfeats 263: 33 K stages
+    [(M, 512, 2048, "lrelu", False) for M in (4116, 4095)] +        # conv3
+    [(4116, 512, 512, "none", False),                                # out_net
+     (4116, 1024, 512, "none", False)] +                             # motion input_emb
+    [(M, 3072, 1024, "none", False) for M in (4116, 84, 1)] +       # motion gi (all steps) / gh (one step)
+    [(4100, 512, 320, "none", False),                                # text input_emb
+     (4100, 1536, 512, "none", False)] +                             # text gi
+    [(M, 300, 32, "none", True) for M in (4100, 100, 1)] +          # word_embs + pos_emb(one-hot): N = 300 into rows of 320 floats
+    [(M, 1024, 2048, "none", False) for M in (84, 1)] +             # motion head, output_net.0
+    [(M, 512, 1024, "none", False) for M in (84, 1)])               # head output_net.3 (motion), output_net.0 (text)
+
+
+@pytest.mark.parametrize("M,N,K,act,padded", EVALUATOR_GEOMETRIES)
+def test_gemm_evaluator_geometries(M, N, K, act, padded):
+    """Against fp64 within trained_like.bound over e32 = the error of torch's fp32 CPU evaluation of the same product (the fixed 2e-5 gate of
+    the tests above was chosen for K <= 1024)."""
+    A, W, b = rnd(M, K), rnd(N, K, scale=1 / math.sqrt(K), seed=1), rnd(N, seed=2)
+    res = rnd(M, N, seed=3) if padded else None
+    want = ref_gemm(A, W, b, res=res, act=act)
+    y32 = {"none": lambda v: v, "lrelu": lambda v: F.leaky_relu(v, 0.2)}[act](F.linear(A, W, b))
+    e32 = ((y32 if res is None else y32 + res).double() - want).abs().max().item()
+    ld = 320 if padded else None
+    got = gemm_ld(A, W, b, res=res, act=act, lda=K, ldy=ld, ldres=ld)[:, :N]
+    err, bd = (got.double() - want).abs().max().item(), bound(e32, want, "fp32")
+    print(f"\n[evaluator gemm] M={M} N={N} K={K} {act}{' res ld320' if padded else ''}: err {err:.3e}  e32 {e32:.3e}  "
+          f"err/e32 {err / max(e32, 1e-30):.2f}  bound {bd:.3e}")
+    assert err <= bd, (M, N, K, act, err, bd)
 
 
 @pytest.mark.parametrize("M", [1, 5, 1280, 25088])
