@@ -252,6 +252,14 @@ LADIFF_API int ladiff_linear_cross_attention(const float* const* w, int layer, c
 LADIFF_API int ladiff_cfg_scheduler_step(const float* eps, float* latents /*[B,T,256] in/out*/, const float* coef,
                               const int32_t* d_step, const float* step_noise /*[n,B,T,256] or NULL*/,
                               float guidance_scale, int cfg, int B, int T, ladiff_stream_t stream);
+/* The multistep form of the same step (DPM-Solver++(2M)): one more term from the PREVIOUS step's data prediction m1,
+ *   {sqrt(a_s), sqrt(1-a_s), k_x0, k_x, k_eps, k_noise, k_m, 0}:  x' = k_x0 x0 + k_x x + k_eps e + k_noise z + k_m m1
+ * x0_prev [B,T,256] (16-byte aligned) holds m1 on entry and this step's x0 on return.  It is read only at a step whose row has
+ * k_m != 0: the first step of a schedule (k_m = 0) may find anything in it, NaN included.  Neither allocates nor synchronises. */
+LADIFF_API int ladiff_cfg_scheduler_step_multistep(const float* eps, float* latents /*[B,T,256] in/out*/,
+                              float* x0_prev /*[B,T,256] in/out*/, const float* coef, const int32_t* d_step,
+                              const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale, int cfg, int B, int T,
+                              ladiff_stream_t stream);
 LADIFF_API int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream);
 
 /* latents[B,T,256] = noise * valid * sigma  (ladiff.py:380-390, :407) */
@@ -381,6 +389,24 @@ LADIFF_API int ladiff_diffusion_reverse_prompts(void* sampler, const float* cons
                              void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales /*[B] device or NULL*/,
                              const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
                              int draw_init_noise, ladiff_stream_t stream);
+/* The same loop with a multistep scheduler (ladiff_cfg_scheduler_step_multistep is its step): x0_prev [B,T,256] device, 16-byte aligned,
+ * carries the previous step's data prediction from step to step, in all three loop forms and across the windows of a long schedule.
+ *   The coefficient table is DEVICE data: the host cannot see whether its column 6 (k_m) is used.  So the pointer selects the form:
+ *   x0_prev set = the multistep form (column 6 is read, the buffer is written at every step); x0_prev NULL = column 6 is ignored, exactly
+ *   ladiff_diffusion_reverse_prompts (which forwards here).
+ *   The buffer is the CALLER's, not part of `ws`: ladiff_reverse_workspace_bytes does not change.  Its contents on entry do not matter
+ *   (row 0 of a multistep table has k_m = 0, and the buffer is not read at such a step); a sampler keys it by pointer. */
+LADIFF_API int ladiff_diffusion_reverse_multistep(void* sampler, const float* const* w, const float* const* w_split /*or NULL*/,
+                             uint64_t weights_generation, const float* text_emb /*[2B or B,n_text,768]*/,
+                             const float* init_noise /*[B,T,256], or NULL with draw_init_noise*/, const int32_t* counts /*[B] or NULL*/,
+                             const int32_t* final_counts /*[B] or NULL*/,
+                             const int32_t* h_counts /*HOST copy of counts, or NULL*/,
+                             const float* sinusoid /*[n,768]*/, const float* coef /*[n,8]*/,
+                             const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale,
+                             float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z /*[T,B,256]*/,
+                             void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales /*[B] device or NULL*/,
+                             const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
+                             int draw_init_noise, float* x0_prev /*[B,T,256] device, or NULL*/, ladiff_stream_t stream);
 /* The per-prompt generator's values as a tensor: out[i][b][t][:] for schedule positions first_step + i of the prompt with key seeds[b]
  * and index prompt_index[b]; first_step = -1 starts at the initial noise.  first_step < -1 is LADIFF_ERR_ARG. */
 LADIFF_API int ladiff_noise_fill_prompts(const uint64_t* seeds /*[B] device*/, const uint32_t* prompt_index /*[B] device or NULL*/,

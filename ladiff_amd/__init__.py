@@ -6,7 +6,7 @@ the `LADIFF`-compatible loop owner.  Arithmetic: libladiff_hip.so (ladiff_amd/cs
 from .feats2joints import Feats2Joints                   # noqa: F401
 from .modules import LADiffDenoiser, LADiffVae          # noqa: F401
 from .pipeline import LADIFF, instantiate_from_config   # noqa: F401
-from .schedulers import DDIMScheduler, DDPMScheduler    # noqa: F401
+from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler    # noqa: F401
 from .text_encoder import MldTextEncoder                # noqa: F401
 from .evaluators import (MovementConvEncoder, MotionEncoderBiGRUCo, TextEncoderBiGRUCo,   # noqa: F401
                          TM2TMetrics, MMMetrics)
@@ -14,5 +14,5 @@ from .evaluation import evaluate, get_metric_statistics, validate   # noqa: F401
 from .joint_metrics import ComputeMetrics, MRMetrics, TemosMetric   # noqa: F401
 from .losses import DiffusionLosses, MLDLosses   # noqa: F401
 
-__all__ = ["LADiffDenoiser", "LADiffVae", "LADIFF", "DDIMScheduler", "DDPMScheduler", "instantiate_from_config", "Feats2Joints", "MldTextEncoder", "MovementConvEncoder", "MotionEncoderBiGRUCo", "TextEncoderBiGRUCo",
+__all__ = ["LADiffDenoiser", "LADiffVae", "LADIFF", "DDIMScheduler", "DDPMScheduler", "DPMSolverMultistepScheduler", "instantiate_from_config", "Feats2Joints", "MldTextEncoder", "MovementConvEncoder", "MotionEncoderBiGRUCo", "TextEncoderBiGRUCo",
            "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics", "validate", "MLDLosses", "DiffusionLosses"]

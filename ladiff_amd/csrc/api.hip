@@ -207,6 +207,13 @@ int ladiff_cfg_scheduler_step(const float* eps, float* latents, const float* coe
     LADIFF_CHECK_ARG(eps && latents && coef && d_step && B > 0 && T > 0);
     return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream));
 }
+int ladiff_cfg_scheduler_step_multistep(const float* eps, float* latents, float* x0_prev, const float* coef, const int32_t* d_step,
+                                        const float* step_noise, float guidance_scale, int cfg, int B, int T, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(eps && latents && x0_prev && coef && d_step && B > 0 && T > 0);
+    if (reinterpret_cast<uintptr_t>(x0_prev) & 15) return LADIFF_ERR_SHAPE;
+    return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream), nullptr, NoiseGen{0u, 0u, 0u, 0},
+                           x0_prev);
+}
 int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(d_step);
     return launch_advance(d_step, S(stream));
@@ -476,6 +483,17 @@ int ladiff_diffusion_reverse_prompts(void* sampler, const float* const* w, const
                                      float guidance_scale, float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z,
                                      void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales, const uint64_t* seeds,
                                      const uint32_t* prompt_index, int draw_init_noise, ladiff_stream_t stream) {
+    return ladiff_diffusion_reverse_multistep(sampler, w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts,
+                                              sinusoid, coef, step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws,
+                                              ws_bytes, reuse_time_tables, guidance_scales, seeds, prompt_index, draw_init_noise, nullptr, stream);
+}
+
+int ladiff_diffusion_reverse_multistep(void* sampler, const float* const* w, const float* const* w_split, uint64_t weights_generation,
+                                       const float* text_emb, const float* init_noise, const int32_t* counts, const int32_t* final_counts,
+                                       const int32_t* h_counts, const float* sinusoid, const float* coef, const float* step_noise,
+                                       float guidance_scale, float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z,
+                                       void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales, const uint64_t* seeds,
+                                       const uint32_t* prompt_index, int draw_init_noise, float* x0_prev, ladiff_stream_t stream) {
     DenoiserW W, WS;
     // what the host can see of the per-prompt arguments, before anything touches the GPU (their VALUES are device data)
     LADIFF_CHECK_ARG(guidance_scales == nullptr || cfg != 0);
@@ -486,12 +504,12 @@ int ladiff_diffusion_reverse_prompts(void* sampler, const float* const* w, const
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
     if (T < 1 || T > LADIFF_MAX_LATENTS || n_text < 1) return LADIFF_ERR_SHAPE;
     if ((reinterpret_cast<uintptr_t>(guidance_scales) & 3) || (reinterpret_cast<uintptr_t>(seeds) & 7) ||
-        (reinterpret_cast<uintptr_t>(prompt_index) & 3))
+        (reinterpret_cast<uintptr_t>(prompt_index) & 3) || (reinterpret_cast<uintptr_t>(x0_prev) & 15))
         return LADIFF_ERR_SHAPE;
     return diffusion_reverse(reinterpret_cast<Sampler*>(sampler), W, w_split ? &WS : nullptr,
                              ReverseArgs{w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid, coef,
                                          step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
-                                         reuse_time_tables, stream, guidance_scales, seeds, prompt_index, draw_init_noise ? 1 : 0});
+                                         reuse_time_tables, stream, guidance_scales, seeds, prompt_index, draw_init_noise ? 1 : 0, x0_prev});
 }
 
 // ------------------------------------------------------------------ LA-VAE encoder

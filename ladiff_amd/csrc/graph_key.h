@@ -12,7 +12,7 @@
 namespace ladiff {
 
 struct GraphKey {
-    static constexpr int CAPACITY = 32;                  // entries; the sampler's key has 30, the decode graph's 20.  One too many aborts.
+    static constexpr int CAPACITY = 32;                  // entries; the sampler's key has 30, 31 with x0_prev, the decode graph's 20.  One too many aborts.
     uint64_t v[CAPACITY] = {0};
     int n = 0;
 
@@ -69,6 +69,8 @@ struct ReverseArgs {
     const uint64_t* seeds;
     const uint32_t* prompt_index;
     int draw_init_noise;                  // the prologue draws the initial noise from `seeds` (schedule position -1) instead of reading init_noise
+    // ladiff_diffusion_reverse_multistep: the caller's [B,T,256] buffer of the previous data prediction, or null (one-step rule)
+    float* x0_prev;
 };
 
 // Key of a sampler's graphs (prologue graph + step graph, or prologue graph + the pipeline's stage table).  n_params: pointers per weight
@@ -79,6 +81,8 @@ struct ReverseArgs {
 // the `pipeline` and `plan_mr` entries (1 and 1 | 2 against 0 and 0) differ between any two such keys.
 // The per-prompt arrays (guidance_scales, seeds, prompt_index) are keyed by POINTER: the prologue graph and the step graphs' tail nodes
 // hold the pointers, the values are read when a graph runs - new scales or seeds in the same buffers replay what is there.
+// x0_prev (the multistep form's state buffer) is baked into the step graphs' tail nodes: keyed by pointer as well, as an entry that only
+// a call with the buffer has - a call without it keys exactly what it keyed before.
 inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, int plan_mr, int plan_nb, const unsigned noise[4]) {
     GraphKey k;
     k.add(a.ws);
@@ -108,6 +112,7 @@ inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, i
     k.add(a.seeds);
     k.add(a.prompt_index);
     k.add(a.draw_init_noise);
+    if (a.x0_prev != nullptr) k.add(a.x0_prev);          // one entry more, so never equal to a key without the buffer (operator== compares n)
     return k;
 }
 

@@ -55,7 +55,7 @@ int one_step(const Call& c, hipStream_t st) {
     LADIFF_TRY(denoiser_forward(c.W, c.WSp, r.tables, r.d_step, r.cache, r.window, r.latents, a.B, c.dup, a.T, a.counts, r.eps, r.fwd,
                                 r.fwd_floats, st, 0, c.B2, 1, a.n_text, r.d_step + 2));
     return launch_step_tail(c.xio, c.xios, c.W.norm.g, c.W.norm.b, r.latents, a.coef, r.d_step, a.step_noise, c.W.query_pe,
-                            a.guidance_scale, a.cfg, a.B, a.T, st, c.gen, a.guidance_scales);
+                            a.guidance_scale, a.cfg, a.B, a.T, st, c.gen, a.guidance_scales, a.x0_prev);
 }
 
 // c-table rows of the window that starts at step `lo` (plain launches, outside the graphs: `lo` changes per window)
@@ -140,7 +140,8 @@ int run_windows(Sampler* sp, const Call& c) {
         if (c.pipeline) {
             LADIFF_TRY(launch_systolic_loop(c.W, r.sys, r.tables, den_cache_tkv(r.cache, c.B2, 1), den_cache_ctab(r.cache, c.B2, 1), r.window,
                                             a.coef, a.step_noise, r.latents, a.counts, a.guidance_scale, a.B, a.T, lo, r.window, c.WSp ? 0 : 1,
-                                            c.plan_mr, c.plan_nb, c.s, a.cfg, sp->fault_wg, sp->timeout_ticks, c.gen, a.guidance_scales));
+                                            c.plan_mr, c.plan_nb, c.s, a.cfg, sp->fault_wg, sp->timeout_ticks, c.gen, a.guidance_scales,
+                                            a.x0_prev));
         } else {
             for (int i = 0; i < r.window / sp->unroll; ++i) LADIFF_HIP(hipGraphLaunch(sp->exec, c.s));
         }

@@ -558,10 +558,12 @@ int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s) {
 }
 
 // Classifier-free guidance + one scheduler step (ladiff.py:487-492), elementwise on [B,T,256].
+// x0p (multistep form, or null): the previous step's data prediction, addressed like lat.  It is read only at a step whose row has
+// k_m != 0 (step-uniform, like the noise branch) and this step's x0 is left in it; null = the one-step rule, column 6 is not read.
 __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ lat,
                                                        const float* __restrict__ coef, const int32_t* __restrict__ d_step,
                                                        const float* __restrict__ noise, float g, const float* __restrict__ gs,
-                                                       int cfg, int T, size_t n4, const NoiseGen gen) {
+                                                       int cfg, int T, size_t n4, const NoiseGen gen, float* __restrict__ x0p) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
     const int step = *d_step;
@@ -584,18 +586,29 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
         noise_normal4(pg, step, prompt, row % T, (int)(i % (D / 4)), zz);
         z = f32x4{zz[0], zz[1], zz[2], zz[3]};
     } else if (noise != nullptr && kn != 0.f) z = ld4(noise + ((size_t)step * n4 + i) * 4);
+    const float km = x0p != nullptr ? c[6] : 0.f;
+    f32x4 m0, m1 = {0.f, 0.f, 0.f, 0.f};
+    if (km != 0.f) m1 = ld4(x0p + i * 4);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const float x0 = (x[k] - sb * e[k]) / sa;
+        m0[k] = x0;
         x[k] = kx0 * x0 + kx * x[k] + ke * e[k] + kn * z[k];
+    }
+    if (x0p != nullptr) {
+        if (km != 0.f) {                 // a statement of its own: the one above keeps its contraction, and m1 is used only where it was loaded
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] += km * m1[k];
+        }
+        st4(x0p + i * 4, m0);
     }
     st4(lat + i * 4, x);
 }
 int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s, const float* gs, const NoiseGen& gen) {
+                    float g, int cfg, int B, int T, hipStream_t s, const float* gs, const NoiseGen& gen, float* x0_prev) {
     const size_t n4 = (size_t)B * T * D / 4;
     hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, coef, d_step, noise, g, gs, cfg, T, n4,
-                       gen);
+                       gen, x0_prev);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }
@@ -610,7 +623,8 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
                                                         const float* __restrict__ nb, float* __restrict__ lat,
                                                         const float* __restrict__ coef, int32_t* __restrict__ d_step,
                                                         const float* __restrict__ noise, const float* __restrict__ pe, float g,
-                                                        const float* __restrict__ gs, int cfg, int B, int T, const NoiseGen gen) {
+                                                        const float* __restrict__ gs, int cfg, int B, int T, const NoiseGen gen,
+                                                        float* __restrict__ x0p) {
     const int step = d_step[0];
     const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);      // row = b * T + t of the B prompts
     const int c = (threadIdx.x & 63) * 4;
@@ -641,14 +655,27 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
             z = f32x4{zz[0], zz[1], zz[2], zz[3]};
         } else if (noise != nullptr && kn != 0.f) z = ld4(noise + ((size_t)step * M + row) * D + c);
         const f32x4 p = ld4(pe + (size_t)(row % T) * D + c);
+        // multistep form (x0p set, cfg_step_kernel): the previous data prediction of the row, only where this step's k_m uses it
+        const float km = x0p != nullptr ? cf[6] : 0.f;
+        f32x4 m0, m1 = {0.f, 0.f, 0.f, 0.f};
+        if (km != 0.f) m1 = ld4(x0p + (size_t)row * D + c);
         f32x4 xn;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float e = cfg ? eu[i] + g * (ec[i] - eu[i]) : eu[i];
             const float x0 = (l[i] - sb * e) / sa;
+            m0[i] = x0;
             l[i] = kx0 * x0 + kx * l[i] + ke * e + kn * z[i];
-            xn[i] = l[i] + p[i];
         }
+        if (x0p != nullptr) {
+            if (km != 0.f) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) l[i] += km * m1[i];
+            }
+            st4(x0p + (size_t)row * D + c, m0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xn[i] = l[i] + p[i];
         st4(lat + (size_t)row * D + c, l);
         st4(x + (size_t)row * D + c, xn);
         if (cfg) st4(x + (size_t)(M + row) * D + c, xn);
@@ -664,10 +691,11 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
     }
 }
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
-                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs) {
+                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs,
+                     float* x0_prev) {
     const int M = B * T;
     hipLaunchKernelGGL(step_tail_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, x, xs, ng, nb, lat, coef,
-                       d_step, noise, pe, g, gs, cfg, B, T, gen);
+                       d_step, noise, pe, g, gs, cfg, B, T, gen, x0_prev);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }

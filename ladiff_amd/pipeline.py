@@ -40,6 +40,7 @@ _TARGET_ALIASES = {
     "ladiff.models.architectures.t2m_motionenc.MotionEncoderBiGRUCo": "ladiff_amd.evaluators.MotionEncoderBiGRUCo",
     "diffusers.DDIMScheduler": "ladiff_amd.schedulers.DDIMScheduler",
     "diffusers.DDPMScheduler": "ladiff_amd.schedulers.DDPMScheduler",
+    "diffusers.DPMSolverMultistepScheduler": "ladiff_amd.schedulers.DPMSolverMultistepScheduler",
 }
 
 
@@ -320,6 +321,10 @@ class LADIFF(nn.Module):
             "tables_key": None,      # weights the time tables inside `ws` were built from
             "sampler": None,
         }
+        if getattr(sch, "multistep", False):
+            # the previous step's data prediction of a multistep scheduler: the loop reads it only at steps whose row uses it (never
+            # at step 0), so it is neither cleared nor copied between calls; every launch of this plan runs the multistep entry
+            plan["x0_prev"] = torch.empty(B, T, 256, dtype=torch.float32, device=dev)
         if self.use_graph:
             h = c_void_p()
             _lib.check(L.ladiff_sampler_create(byref(h)))
@@ -536,7 +541,10 @@ class LADIFF(nn.Module):
         def enqueue(loop):
             if sampler is not None:
                 _lib.check(L.ladiff_sampler_set_loop(sampler, loop_codes[loop]))
-            _lib.check(L.ladiff_diffusion_reverse_prompts(
+            x0_prev = plan.get("x0_prev")
+            entry = L.ladiff_diffusion_reverse_prompts if x0_prev is None else L.ladiff_diffusion_reverse_multistep
+            tail = (run.cuda_stream,) if x0_prev is None else (_lib.ptr(x0_prev), run.cuda_stream)
+            _lib.check(entry(
                 sampler, wt.array,
                 wt.split_array() if _lib.is_split(self.precision) else None, wt.generation, _lib.ptr(plan["text"]),
                 None if draw_init else _lib.ptr(plan["noise"]),
@@ -548,7 +556,7 @@ class LADIFF(nn.Module):
                 self.guidance_scale if per.get("scalar_g") is None else per["scalar_g"], float(sch.init_noise_sigma), 1 if cfg else 0, B, T,
                 n_text, n, _lib.ptr(plan["z"]), _lib.ptr(plan["ws"]), plan["ws_bytes"], 1 if plan["tables_key"] == wt.key else 0,
                 None if gscales is None else _lib.ptr(plan["gscales"]), None if seeds is None else plan["seeds"].data_ptr(),
-                None if pindex is None else plan["pindex"].data_ptr(), 1 if draw_init else 0, run.cuda_stream))
+                None if pindex is None else plan["pindex"].data_ptr(), 1 if draw_init else 0, *tail))
             plan["tables_key"] = wt.key
             # the loop's status words follow it on the stream into pinned memory: 8 bytes, no host synchronisation here
             slot = plan["launches"] % 8

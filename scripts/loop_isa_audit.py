@@ -6,7 +6,7 @@ usage: loop_isa_audit.py [kernel-name substring, default the headline instantiat
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-key = sys.argv[1] if len(sys.argv) > 1 else "systolic_loop_kernelILi1ELi0ELi2ELi1ELb1E"
+key = sys.argv[1] if len(sys.argv) > 1 else "systolic_loop_kernelILi1ELi0ELi2ELi1ELb1ELb0E"
 stem = sys.argv[2] if len(sys.argv) > 2 else "systolic"
 builddir = os.environ.get("LADIFF_OBJDIR", os.path.join(ROOT, "ladiff_amd", "csrc", "build"))
 with tempfile.TemporaryDirectory() as tmp:
