@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "libladiff_hip.so")
 MAX_LATENTS = 8
 MAX_FRAMES = 224
 COEF_STRIDE = 8
+COEF_K_NOISE, COEF_K_M = 5, 6      # columns of a coefficient row that Python reads or places by index (csrc/step_rule.h names all seven)
 ACT = {"none": 0, "relu": 1, "gelu": 2, "silu": 3, "qgelu": 4, "lrelu": 5}
 
 

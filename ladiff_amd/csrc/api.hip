@@ -211,7 +211,7 @@ int ladiff_cfg_scheduler_step_multistep(const float* eps, float* latents, float*
                                         const float* step_noise, float guidance_scale, int cfg, int B, int T, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(eps && latents && x0_prev && coef && d_step && B > 0 && T > 0);
     if (reinterpret_cast<uintptr_t>(x0_prev) & 15) return LADIFF_ERR_SHAPE;
-    return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream), nullptr, NoiseGen{0u, 0u, 0u, 0},
+    return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream), NoiseGen{0u, 0u, 0u, 0}, nullptr,
                            x0_prev);
 }
 int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream) {

@@ -52,13 +52,12 @@ int launch_zero_fill(float* x, size_t n, hipStream_t s);          // kernel, not
 int launch_silu(const float* x, float* y, size_t n, hipStream_t s);
 int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s);
 int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s, const float* gs = nullptr, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
-                    float* x0_prev = nullptr);            // x0_prev: [B,T,256] previous data prediction (multistep form), or null
+                    float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
+                    const float* gs = nullptr, float* x0_prev = nullptr);   // gs: [B] per-prompt scales (device) instead of g; x0_prev: [B,T,256] previous data prediction (multistep form), or null
 int launch_advance(int32_t* d_step, hipStream_t s);
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
                      const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
-                     const float* gs = nullptr,            // gs: [B] per-prompt guidance scales (device) instead of g
-                     float* x0_prev = nullptr);            // as for launch_cfg_step
+                     const float* gs = nullptr, float* x0_prev = nullptr);            // as for launch_cfg_step
 int launch_noise_fill(const NoiseGen& gen, int step0, int n, int B, int T, float* out, hipStream_t s);
 int launch_init_latents(const float* noise, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);
 int launch_init_latents_gen(const NoiseGen& gen, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);   // gen.seeds set

@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "step_rule.h"
 
 namespace ladiff {
 
@@ -569,43 +570,17 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     const int step = *d_step;
     const int row = (int)(i / (D / 4));                                  // row = b * T + t
     if (gs != nullptr) g = gs[row / T];                                  // the prompt's own scale (launch-uniform branch)
-    const float* c = coef + (size_t)step * LADIFF_COEF_STRIDE;
-    const float sa = c[0], sb = c[1], kx0 = c[2], kx = c[3], ke = c[4], kn = c[5];
+    const StepCoef c = step_coef(coef, step, x0p != nullptr);
     f32x4 e = ld4(eps + i * 4);
-    if (cfg) {
-        const f32x4 ec = ld4(eps + (n4 + i) * 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) e[k] = e[k] + g * (ec[k] - e[k]);
-    }
+    if (cfg) e = guide4(e, ld4(eps + (n4 + i) * 4), g);
     f32x4 x = ld4(lat + i * 4);
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    if (gen.on && kn != 0.f) {
-        float zz[4];
-        unsigned prompt;
-        const NoiseGen pg = noise_of_prompt(gen, row / T, prompt);
-        noise_normal4(pg, step, prompt, row % T, (int)(i % (D / 4)), zz);
-        z = f32x4{zz[0], zz[1], zz[2], zz[3]};
-    } else if (noise != nullptr && kn != 0.f) z = ld4(noise + ((size_t)step * n4 + i) * 4);
-    const float km = x0p != nullptr ? c[6] : 0.f;
-    f32x4 m0, m1 = {0.f, 0.f, 0.f, 0.f};
-    if (km != 0.f) m1 = ld4(x0p + i * 4);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float x0 = (x[k] - sb * e[k]) / sa;
-        m0[k] = x0;
-        x[k] = kx0 * x0 + kx * x[k] + ke * e[k] + kn * z[k];
-    }
-    if (x0p != nullptr) {
-        if (km != 0.f) {                 // a statement of its own: the one above keeps its contraction, and m1 is used only where it was loaded
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x[k] += km * m1[k];
-        }
-        st4(x0p + i * 4, m0);
-    }
+    const f32x4 z = step_noise4(gen, noise, c.kn, step, row / T, row % T, (int)(i % (D / 4)), ((size_t)step * n4 + i) * 4);
+    const f32x4 m0 = step_rule4(x, e, z, x0p + i * 4, c);
+    if (x0p != nullptr) st4(x0p + i * 4, m0);
     st4(lat + i * 4, x);
 }
 int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s, const float* gs, const NoiseGen& gen, float* x0_prev) {
+                    float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs, float* x0_prev) {
     const size_t n4 = (size_t)B * T * D / 4;
     hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, coef, d_step, noise, g, gs, cfg, T, n4,
                        gen, x0_prev);
@@ -630,8 +605,7 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
     const int c = (threadIdx.x & 63) * 4;
     const int M = B * T;
     if (row < M) {
-        const float* cf = coef + (size_t)step * LADIFF_COEF_STRIDE;
-        const float sa = cf[0], sb = cf[1], kx0 = cf[2], kx = cf[3], ke = cf[4], kn = cf[5];
+        const StepCoef cf = step_coef(coef, step, x0p != nullptr);
         if (gs != nullptr) g = gs[row / T];                                // the prompt's own scale (launch-uniform branch)
         const f32x4 gg = ld4(ng + c), bb = ld4(nb + c);
         f32x4 eu = ld4(x + (size_t)row * D + c), ec = eu;
@@ -646,31 +620,23 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
             for (int i = 0; i < 4; ++i) ec[i] = (ec[i] - mean) * rstd * gg[i] + bb[i];
         }
         f32x4 l = ld4(lat + (size_t)row * D + c);
-        f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        if (gen.on && kn != 0.f) {       // drawn here (noise_gen.h): the same function of (seed, step, global prompt, latent, column) as everywhere
-            float zz[4];
-            unsigned prompt;
-            const NoiseGen pg = noise_of_prompt(gen, row / T, prompt);
-            noise_normal4(pg, step, prompt, row % T, c / 4, zz);
-            z = f32x4{zz[0], zz[1], zz[2], zz[3]};
-        } else if (noise != nullptr && kn != 0.f) z = ld4(noise + ((size_t)step * M + row) * D + c);
+        const f32x4 z = step_noise4(gen, noise, cf.kn, step, row / T, row % T, c / 4, ((size_t)step * M + row) * D + c);
         const f32x4 p = ld4(pe + (size_t)(row % T) * D + c);
         // multistep form (x0p set, cfg_step_kernel): the previous data prediction of the row, only where this step's k_m uses it
-        const float km = x0p != nullptr ? cf[6] : 0.f;
         f32x4 m0, m1 = {0.f, 0.f, 0.f, 0.f};
-        if (km != 0.f) m1 = ld4(x0p + (size_t)row * D + c);
+        if (cf.km != 0.f) m1 = ld4(x0p + (size_t)row * D + c);
         f32x4 xn;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i) {        // guide4 + step_rule4 (step_rule.h) written out: DESIGN 8g says why this launch keeps its own copy
             const float e = cfg ? eu[i] + g * (ec[i] - eu[i]) : eu[i];
-            const float x0 = (l[i] - sb * e) / sa;
+            const float x0 = (l[i] - cf.sb * e) / cf.sa;
             m0[i] = x0;
-            l[i] = kx0 * x0 + kx * l[i] + ke * e + kn * z[i];
+            l[i] = cf.kx0 * x0 + cf.kx * l[i] + cf.ke * e + cf.kn * z[i];
         }
         if (x0p != nullptr) {
-            if (km != 0.f) {
+            if (cf.km != 0.f) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) l[i] += km * m1[i];
+                for (int i = 0; i < 4; ++i) l[i] += cf.km * m1[i];
             }
             st4(x0p + (size_t)row * D + c, m0);
         }

@@ -53,6 +53,7 @@
 #include <vector>
 
 #include "model.h"
+#include "step_rule.h"
 #include "tile_mma.h"
 
 namespace ladiff {
@@ -1985,15 +1986,13 @@ struct TailRole {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = 4 * lane;
         const unsigned bu = (unsigned)blk_u(u) * RT * 1024, bc = (unsigned)blk_c(u) * RT * 1024;
         const int step = p.step_lo + s;
-        const float kn = p.coef[(size_t)step * LADIFF_COEF_STRIDE + 5];
-        float km = 0.f;
-        if constexpr (MS) km = p.coef[(size_t)step * LADIFF_COEF_STRIDE + 6];
+        const StepCoef cf = step_coef(p.coef, step, MS);                 // k_noise and k_m: what this step reads at all
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
             const int q = wave + NW * i;
             y.zz[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (g.lat[i] >= 0) {
-                if constexpr (MS) { if (km != 0.f) y.m1[i] = ld4(p.x0p + (size_t)g.lat[i] * D + c); }
+                if constexpr (MS) { if (cf.km != 0.f) y.m1[i] = ld4(p.x0p + (size_t)g.lat[i] * D + c); }
                 y.eu[i] = ld_sc1(rin, bu + q * 1024 + c * 4);
                 y.ec[i] = ld_sc1(rin, bc + g.rc[i] * 1024 + c * 4);
                 y.lt[i] = ld4(p.lat + (size_t)g.lat[i] * D + c);
@@ -2002,13 +2001,7 @@ struct TailRole {
                 // launch, and a launch without the arrays divides nowhere it did not before
                 y.gs[i] = p.gscale;
                 if (p.gscales != nullptr) y.gs[i] = p.gscales[g.lat[i] / T];
-                if (p.gen.on && kn != 0.f) {
-                    float zz[4];
-                    unsigned prompt;
-                    const NoiseGen pg = noise_of_prompt(p.gen, g.lat[i] / T, prompt);
-                    noise_normal4(pg, step, prompt, g.t[i], lane, zz);
-                    y.zz[i] = f32x4{zz[0], zz[1], zz[2], zz[3]};
-                } else if (p.noise != nullptr && kn != 0.f) y.zz[i] = ld4(p.noise + ((size_t)step * p.B * T + g.lat[i]) * D + c);
+                y.zz[i] = step_noise4(p.gen, p.noise, cf.kn, step, g.lat[i] / T, g.t[i], lane, ((size_t)step * p.B * T + g.lat[i]) * D + c);
             } else if (HO) {                                             // the tickets of a slot that only pads (Red2Role::issue)
                 if (g.pad[i] >= 0) y.eu[i] = ld_sc1(rin, bu + g.pad[i] * 1024 + c * 4);
                 if (g.rc[i] >= 0) y.ec[i] = ld_sc1(rin, bc + g.rc[i] * 1024 + c * 4);
@@ -2018,15 +2011,12 @@ struct TailRole {
     __device__ __forceinline__ void compute(int s, int u, const Geo& g, Pay& y) {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = 4 * lane;
         const unsigned bu = (unsigned)blk_u(u) * RT * 1024, bc = (unsigned)blk_c(u) * RT * 1024;
-        const float* cf = p.coef + (size_t)(p.step_lo + s) * LADIFF_COEF_STRIDE;
-        const float sa = cf[0], sb = cf[1], kx0 = cf[2], kx = cf[3], ke = cf[4], kn = cf[5];
-        float km = 0.f;
-        if constexpr (MS) km = cf[6];
+        const StepCoef cf = step_coef(p.coef, p.step_lo + s, MS);          // MS == false: k_m is the literal 0 and its branch folds away
 #pragma unroll
         for (int i = 0; i < NQ; ++i) {
             const int q = wave + NW * i;
             if (g.lat[i] >= 0) {
-                f32x4 eu = untag4(y.eu[i]), ec = untag4(y.ec[i]), l = y.lt[i], xn, m0;
+                f32x4 eu = untag4(y.eu[i]), ec = untag4(y.ec[i]), l = y.lt[i], xn;
                 float mean, rstd;
                 row_stats4(eu, mean, rstd);
 #pragma unroll
@@ -2034,20 +2024,8 @@ struct TailRole {
                 row_stats4(ec, mean, rstd);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) ec[k] = (ec[k] - mean) * rstd * gg[k] + bb[k];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float e = eu[k] + y.gs[i] * (ec[k] - eu[k]);
-                    const float x0 = (l[k] - sb * e) / sa;
-                    m0[k] = x0;
-                    l[k] = kx0 * x0 + kx * l[k] + ke * e + kn * y.zz[i][k];
-                }
-                if constexpr (MS) {              // the statement above is the one-step rule as it was; m1 is used only where it was loaded
-                    if (km != 0.f) {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) l[k] += km * y.m1[i][k];
-                    }
-                    st4(p.x0p + (size_t)g.lat[i] * D + c, m0);
-                }
+                const f32x4 m0 = step_rule4(l, guide4(eu, ec, y.gs[i]), y.zz[i], reinterpret_cast<const float*>(&y.m1[MS ? i : 0]), cf);     // read only where `issue` loaded it
+                if constexpr (MS) st4(p.x0p + (size_t)g.lat[i] * D + c, m0);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) xn[k] = l[k] + y.pe[i][k];
                 st4(p.lat + (size_t)g.lat[i] * D + c, l);

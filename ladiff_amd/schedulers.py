@@ -67,7 +67,7 @@ class _Scheduler:
         return tab
 
     def needs_noise(self, eta=0.0):
-        return bool((self.coef_table(eta)[:, 5] != 0).any())
+        return bool((self.coef_table(eta)[:, _lib.COEF_K_NOISE] != 0).any())
 
     # ---- single step on the GPU (drop-in for `scheduler.step(...).prev_sample`, ladiff.py:491-492)
     def _step(self, model_output, timestep, sample, eta, variance_noise):
@@ -81,7 +81,7 @@ class _Scheduler:
             self._step_dev = {key: torch.arange(len(self.timesteps), dtype=torch.int32, device=sample.device)}
         coef, steps = self._coef_dev[key], self._step_dev[key]
         i = int(idx[0])
-        if coef[i, 5].item() != 0 and variance_noise is None:
+        if coef[i, _lib.COEF_K_NOISE].item() != 0 and variance_noise is None:
             variance_noise = torch.randn_like(sample)
         out = sample.detach().to(torch.float32).contiguous().clone()
         eps = model_output.detach().to(torch.float32).contiguous()
@@ -280,7 +280,8 @@ class DPMSolverMultistepScheduler(_Scheduler):
             if orders[i] == 2:
                 r0 = (lam[i] - lam[i - 1]) / h
                 k_x0, k_m = A * (1.0 + 0.5 / r0), -A * 0.5 / r0
-            tab[i] = torch.tensor([alpha[i], sigma[i], k_x0, k_x, 0.0, 0.0, k_m, 0.0], dtype=torch.float64)
+            tab[i, :4] = torch.tensor([alpha[i], sigma[i], k_x0, k_x], dtype=torch.float64)      # k_eps = k_noise = 0
+            tab[i, _lib.COEF_K_M] = k_m
         return tab.to(torch.float32)
 
     def needs_noise(self, eta=0.0):
@@ -315,7 +316,7 @@ class DPMSolverMultistepScheduler(_Scheduler):
                              f"model_output {tuple(model_output.shape)}")
         fresh = self._x0_prev is None or self._x0_prev.shape != out.shape or self._x0_prev.device != out.device
         if fresh:
-            if float(self._coef_host[i, 6]) != 0.0:
+            if float(self._coef_host[i, _lib.COEF_K_M]) != 0.0:
                 raise ValueError(f"step {i} of the schedule is a second-order step and no previous step of this shape was taken")
             self._x0_prev = torch.empty_like(out)           # not read at a step whose k_m is zero
         _lib.check(_lib.lib().ladiff_cfg_scheduler_step_multistep(_lib.ptr(eps), _lib.ptr(out), _lib.ptr(self._x0_prev), _lib.ptr(coef),
