@@ -260,11 +260,29 @@ LADIFF_API int ladiff_cfg_scheduler_step_multistep(const float* eps, float* late
                               float* x0_prev /*[B,T,256] in/out*/, const float* coef, const int32_t* d_step,
                               const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale, int cfg, int B, int T,
                               ladiff_stream_t stream);
+/* The same step in a loop that starts from a source motion (ladiff_diffusion_reverse_from): prompt b enters the schedule at position
+ * s_b = starts[b] ([B] int32 device; NULL: s_b = first_step).  At position s = *d_step a row of prompt b is
+ *   s <  s_b  frozen: the latent row keeps its bits, x0_prev is neither read nor written, no noise is used;
+ *   s == s_b  in the multistep form first order: k_x0 + k_m stands in for k_x0 and m1 is not read (A (1 + 1/(2 r0)) - A/(2 r0) = A);
+ *   otherwise the rule above.
+ * x0_prev may be NULL: the one-step rule. */
+LADIFF_API int ladiff_cfg_scheduler_step_from(const float* eps, float* latents /*[B,T,256] in/out*/,
+                              float* x0_prev /*[B,T,256] in/out, or NULL*/, const float* coef, const int32_t* d_step,
+                              const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale, int cfg, int B, int T,
+                              const int32_t* starts /*[B] device or NULL*/, int first_step, ladiff_stream_t stream);
 LADIFF_API int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream);
 
 /* latents[B,T,256] = noise * valid * sigma  (ladiff.py:380-390, :407) */
 LADIFF_API int ladiff_init_latents(const float* noise, const int32_t* counts, float init_noise_sigma, float* latents,
                         int B, int T, ladiff_stream_t stream);
+/* Initial latents of a loop from a source motion, one kernel:
+ *   latents[b,t,:] = valid(b,t) (coef[s_b][0] z0[t,b,:] + coef[s_b][1] noise[b,t,:]),  s_b = starts[b] or first_step
+ * = scheduler.add_noise(z0, noise, timesteps[s_b]).  z0 is [T,B,256], the layout of the loop's z and of the encoder's output.  noise is a
+ * [B,T,256] tensor, or NULL: the per-prompt generator (seeds, prompt_index) at position -1, as the loop's draw_init_noise draws it. */
+LADIFF_API int ladiff_init_latents_from(const float* z0 /*[T,B,256]*/, const float* noise /*[B,T,256] or NULL*/,
+                              const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
+                              const int32_t* counts /*[B] or NULL*/, const float* coef /*[n,8]*/, const int32_t* starts /*[B] device or NULL*/,
+                              int first_step, float* latents /*[B,T,256]*/, int B, int T, ladiff_stream_t stream);
 /* z[T,B,256] = permute(latents) with rows >= counts[b] zeroed  (ladiff.py:500, :562-566).  (Inside
  * ladiff_diffusion_reverse the same kernel also reads the pipeline's abort word and writes NaN when the loop was abandoned.) */
 LADIFF_API int ladiff_finalize_latents(const float* latents, const int32_t* counts, float* z, int B, int T,
@@ -407,6 +425,29 @@ LADIFF_API int ladiff_diffusion_reverse_multistep(void* sampler, const float* co
                              void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales /*[B] device or NULL*/,
                              const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
                              int draw_init_noise, float* x0_prev /*[B,T,256] device, or NULL*/, ladiff_stream_t stream);
+/* The same loop from a SOURCE MOTION (SDEdit): z0 [T,B,256] device, 16-byte aligned, is noised to each prompt's own schedule position
+ * and denoised from there.  Positions first_step .. n_steps - 1 run exactly once each (0 <= first_step < n_steps, else LADIFF_ERR_ARG);
+ * time-table rows, c-table windows, sinusoid rows and noise positions keep their full-schedule indices.  starts [B] int32 device or NULL:
+ * prompt b starts at s_b = starts[b], NULL = first_step for all.  The values are device data: first_step <= starts[b] < n_steps is the
+ * CALLER's contract.  starts without z0 is LADIFF_ERR_ARG.
+ *   The prologue writes latents = valid (coef[s_b][0] z0 + coef[s_b][1] noise) (ladiff_init_latents_from) with noise = init_noise or, with
+ *   draw_init_noise, the per-prompt generator at position -1; init_noise_sigma is not applied.  Every step ends as
+ *   ladiff_cfg_scheduler_step_from describes.  Nothing mixes prompts: a prompt's result depends on its own (text, z0, s_b, seed, index, scale).
+ *   z0 NULL = ladiff_diffusion_reverse_multistep exactly (which forwards here; first_step must then be 0).  z0 and starts are the caller's
+ *   buffers, keyed by pointer; first_step is part of a sampler's key in the launch-per-stage form and in a call without starts, a launch
+ *   argument otherwise.  n_text > 1 with z0 is LADIFF_ERR_UNSUPPORTED. */
+LADIFF_API int ladiff_diffusion_reverse_from(void* sampler, const float* const* w, const float* const* w_split /*or NULL*/,
+                             uint64_t weights_generation, const float* text_emb /*[2B or B,n_text,768]*/,
+                             const float* init_noise /*[B,T,256], or NULL with draw_init_noise*/, const int32_t* counts /*[B] or NULL*/,
+                             const int32_t* final_counts /*[B] or NULL*/,
+                             const int32_t* h_counts /*HOST copy of counts, or NULL*/,
+                             const float* sinusoid /*[n,768]*/, const float* coef /*[n,8]*/,
+                             const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale,
+                             float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z /*[T,B,256]*/,
+                             void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales /*[B] device or NULL*/,
+                             const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
+                             int draw_init_noise, float* x0_prev /*[B,T,256] device, or NULL*/, const float* z0 /*[T,B,256] device, or NULL*/,
+                             const int32_t* starts /*[B] device or NULL*/, int first_step, ladiff_stream_t stream);
 /* The per-prompt generator's values as a tensor: out[i][b][t][:] for schedule positions first_step + i of the prompt with key seeds[b]
  * and index prompt_index[b]; first_step = -1 starts at the initial noise.  first_step < -1 is LADIFF_ERR_ARG. */
 LADIFF_API int ladiff_noise_fill_prompts(const uint64_t* seeds /*[B] device*/, const uint32_t* prompt_index /*[B] device or NULL*/,

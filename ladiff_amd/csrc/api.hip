@@ -214,6 +214,14 @@ int ladiff_cfg_scheduler_step_multistep(const float* eps, float* latents, float*
     return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream), NoiseGen{0u, 0u, 0u, 0}, nullptr,
                            x0_prev);
 }
+int ladiff_cfg_scheduler_step_from(const float* eps, float* latents, float* x0_prev, const float* coef, const int32_t* d_step,
+                                   const float* step_noise, float guidance_scale, int cfg, int B, int T, const int32_t* starts, int first_step,
+                                   ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(eps && latents && coef && d_step && B > 0 && T > 0 && first_step >= 0);
+    if ((reinterpret_cast<uintptr_t>(x0_prev) & 15) || (reinterpret_cast<uintptr_t>(starts) & 3)) return LADIFF_ERR_SHAPE;
+    return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream), NoiseGen{0u, 0u, 0u, 0}, nullptr,
+                           x0_prev, true, starts, first_step);
+}
 int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(d_step);
     return launch_advance(d_step, S(stream));
@@ -222,6 +230,18 @@ int ladiff_init_latents(const float* noise, const int32_t* counts, float sigma, 
                         ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(noise && latents && B > 0 && T > 0);
     return launch_init_latents(noise, counts, sigma, latents, B, T, S(stream));
+}
+int ladiff_init_latents_from(const float* z0, const float* noise, const uint64_t* seeds, const uint32_t* prompt_index, const int32_t* counts,
+                             const float* coef, const int32_t* starts, int first_step, float* latents, int B, int T, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(z0 && coef && latents && B > 0 && T > 0 && first_step >= 0);
+    LADIFF_CHECK_ARG(noise != nullptr || seeds != nullptr);
+    LADIFF_CHECK_ARG(prompt_index == nullptr || seeds != nullptr);
+    if ((reinterpret_cast<uintptr_t>(z0) & 15) || (reinterpret_cast<uintptr_t>(noise) & 15) || (reinterpret_cast<uintptr_t>(latents) & 15) ||
+        (reinterpret_cast<uintptr_t>(seeds) & 7) || (reinterpret_cast<uintptr_t>(prompt_index) & 3) || (reinterpret_cast<uintptr_t>(starts) & 3))
+        return LADIFF_ERR_SHAPE;
+    const NoiseGen gen = noise == nullptr ? NoiseGen{0u, 0u, 0u, 1, reinterpret_cast<const unsigned long long*>(seeds), prompt_index}
+                                          : NoiseGen{0u, 0u, 0u, 0};
+    return launch_init_latents_from(z0, noise, gen, counts, coef, starts, first_step, latents, B, T, nullptr, S(stream));
 }
 int ladiff_finalize_latents(const float* latents, const int32_t* counts, float* z, int B, int T, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(latents && z && B > 0 && T > 0);
@@ -494,7 +514,23 @@ int ladiff_diffusion_reverse_multistep(void* sampler, const float* const* w, con
                                        float guidance_scale, float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z,
                                        void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales, const uint64_t* seeds,
                                        const uint32_t* prompt_index, int draw_init_noise, float* x0_prev, ladiff_stream_t stream) {
+    return ladiff_diffusion_reverse_from(sampler, w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid,
+                                         coef, step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
+                                         reuse_time_tables, guidance_scales, seeds, prompt_index, draw_init_noise, x0_prev, nullptr, nullptr, 0,
+                                         stream);
+}
+
+int ladiff_diffusion_reverse_from(void* sampler, const float* const* w, const float* const* w_split, uint64_t weights_generation,
+                                  const float* text_emb, const float* init_noise, const int32_t* counts, const int32_t* final_counts,
+                                  const int32_t* h_counts, const float* sinusoid, const float* coef, const float* step_noise,
+                                  float guidance_scale, float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z,
+                                  void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales, const uint64_t* seeds,
+                                  const uint32_t* prompt_index, int draw_init_noise, float* x0_prev, const float* z0, const int32_t* starts,
+                                  int first_step, ladiff_stream_t stream) {
     DenoiserW W, WS;
+    // a loop from a source motion: `starts` means nothing without z0, and the first position is one of the schedule's
+    LADIFF_CHECK_ARG(starts == nullptr || z0 != nullptr);
+    LADIFF_CHECK_ARG(first_step >= 0 && (first_step < n_steps || n_steps <= 0) && (z0 != nullptr || first_step == 0));
     // what the host can see of the per-prompt arguments, before anything touches the GPU (their VALUES are device data)
     LADIFF_CHECK_ARG(guidance_scales == nullptr || cfg != 0);
     LADIFF_CHECK_ARG(prompt_index == nullptr || seeds != nullptr);
@@ -504,12 +540,15 @@ int ladiff_diffusion_reverse_multistep(void* sampler, const float* const* w, con
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
     if (T < 1 || T > LADIFF_MAX_LATENTS || n_text < 1) return LADIFF_ERR_SHAPE;
     if ((reinterpret_cast<uintptr_t>(guidance_scales) & 3) || (reinterpret_cast<uintptr_t>(seeds) & 7) ||
-        (reinterpret_cast<uintptr_t>(prompt_index) & 3) || (reinterpret_cast<uintptr_t>(x0_prev) & 15))
+        (reinterpret_cast<uintptr_t>(prompt_index) & 3) || (reinterpret_cast<uintptr_t>(x0_prev) & 15) ||
+        (reinterpret_cast<uintptr_t>(z0) & 15) || (reinterpret_cast<uintptr_t>(starts) & 3))
         return LADIFF_ERR_SHAPE;
+    if (z0 != nullptr && n_text != 1) return LADIFF_ERR_UNSUPPORTED;      // the text-sequence form has no loop from a source motion
     return diffusion_reverse(reinterpret_cast<Sampler*>(sampler), W, w_split ? &WS : nullptr,
                              ReverseArgs{w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid, coef,
                                          step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
-                                         reuse_time_tables, stream, guidance_scales, seeds, prompt_index, draw_init_noise ? 1 : 0, x0_prev});
+                                         reuse_time_tables, stream, guidance_scales, seeds, prompt_index, draw_init_noise ? 1 : 0, x0_prev, z0,
+                                         z0 != nullptr ? starts : nullptr, z0 != nullptr ? first_step : 0});
 }
 
 // ------------------------------------------------------------------ LA-VAE encoder

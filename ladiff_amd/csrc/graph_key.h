@@ -12,7 +12,7 @@
 namespace ladiff {
 
 struct GraphKey {
-    static constexpr int CAPACITY = 32;                  // entries; the sampler's key has 30, 31 with x0_prev, the decode graph's 20.  One too many aborts.
+    static constexpr int CAPACITY = 36;                  // entries; the sampler's key has 30, 31 with x0_prev, up to 34 with z0 / starts / first_step, the decode graph's 20.  One too many aborts.
     uint64_t v[CAPACITY] = {0};
     int n = 0;
 
@@ -71,6 +71,11 @@ struct ReverseArgs {
     int draw_init_noise;                  // the prologue draws the initial noise from `seeds` (schedule position -1) instead of reading init_noise
     // ladiff_diffusion_reverse_multistep: the caller's [B,T,256] buffer of the previous data prediction, or null (one-step rule)
     float* x0_prev;
+    // ladiff_diffusion_reverse_from: the loop starts from source latents z0 [T,B,256] noised to each prompt's own schedule position
+    // (starts [B] device, or null: all at first_step); positions first_step .. n_steps - 1 run.  z0 null: neither is looked at.
+    const float* z0 = nullptr;
+    const int32_t* starts = nullptr;
+    int first_step = 0;
 };
 
 // Key of a sampler's graphs (prologue graph + step graph, or prologue graph + the pipeline's stage table).  n_params: pointers per weight
@@ -83,6 +88,11 @@ struct ReverseArgs {
 // hold the pointers, the values are read when a graph runs - new scales or seeds in the same buffers replay what is there.
 // x0_prev (the multistep form's state buffer) is baked into the step graphs' tail nodes: keyed by pointer as well, as an entry that only
 // a call with the buffer has - a call without it keys exactly what it keyed before.
+// z0 / starts (ladiff_diffusion_reverse_from): the prologue graph and the step graphs' tail nodes hold the pointers, the pipeline kernel takes
+// them as launch arguments next to the captured prologue: keyed by pointer under a marker entry, again entries that only such a call has.
+// first_step is baked in where a captured node holds it: the launch-per-stage form (its prologue sets the step counter) and a call without
+// `starts` (the prologue kernel noises every prompt to first_step).  A pipeline call with `starts` passes it as a launch argument only: not
+// keyed, new starts or a new first_step replay what is there.
 inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, int plan_mr, int plan_nb, const unsigned noise[4]) {
     GraphKey k;
     k.add(a.ws);
@@ -113,6 +123,11 @@ inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, i
     k.add(a.prompt_index);
     k.add(a.draw_init_noise);
     if (a.x0_prev != nullptr) k.add(a.x0_prev);          // one entry more, so never equal to a key without the buffer (operator== compares n)
+    if (a.z0 != nullptr) {
+        k.add(a.z0);
+        k.add(a.starts);
+        k.add(!pipeline || a.starts == nullptr ? a.first_step : -1);
+    }
     return k;
 }
 

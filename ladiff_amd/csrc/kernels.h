@@ -53,14 +53,19 @@ int launch_silu(const float* x, float* y, size_t n, hipStream_t s);
 int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s);
 int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
                     float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
-                    const float* gs = nullptr, float* x0_prev = nullptr);   // gs: [B] per-prompt scales (device) instead of g; x0_prev: [B,T,256] previous data prediction (multistep form), or null
+                    const float* gs = nullptr, float* x0_prev = nullptr, bool edit = false, const int32_t* starts = nullptr,
+                    int first_step = 0);   // edit: prompt b enters the schedule at starts[b] (null: first_step), step_gate in step_rule.h; gs: [B] per-prompt scales (device) instead of g; x0_prev: [B,T,256] previous data prediction (multistep form), or null
 int launch_advance(int32_t* d_step, hipStream_t s);
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
                      const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
-                     const float* gs = nullptr, float* x0_prev = nullptr);            // as for launch_cfg_step
+                     const float* gs = nullptr, float* x0_prev = nullptr, bool edit = false, const int32_t* starts = nullptr,
+                     int first_step = 0);            // as for launch_cfg_step
 int launch_noise_fill(const NoiseGen& gen, int step0, int n, int B, int T, float* out, hipStream_t s);
 int launch_init_latents(const float* noise, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);
 int launch_init_latents_gen(const NoiseGen& gen, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);   // gen.seeds set
+// latents = valid (alpha(s_b) z0 + sigma(s_b) noise): z0 [T,B,256]; noise null = gen at position -1; d_step (or null) is left at {first_step, 0, 0, 0}
+int launch_init_latents_from(const float* z0, const float* noise, const NoiseGen& gen, const int32_t* counts, const float* coef,
+                             const int32_t* starts, int first_step, float* lat, int B, int T, int32_t* d_step, hipStream_t s);
 int launch_finalize_latents(const float* lat, const int32_t* counts, float* z, int B, int T, hipStream_t s, const unsigned* status = nullptr);
 
 int launch_dec_qkv_attn(const float* xs, const float* w, const float* bias, const int32_t* lengths, const int32_t* row_off, float* out,

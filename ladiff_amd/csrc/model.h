@@ -99,7 +99,8 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
                          int step_lo, int n, int fp32, int MR, int NB, hipStream_t s, int cfg = 1, int fault_wg = -1,
                          unsigned long long timeout_ticks = 0, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
                          const float* gscales = nullptr,       // [B] per-prompt guidance scales (device) instead of gscale
-                         float* x0_prev = nullptr);            // [B,T,256] previous data prediction (multistep form), or null
+                         float* x0_prev = nullptr,             // [B,T,256] previous data prediction (multistep form), or null
+                         bool edit = false, const int32_t* starts = nullptr, int first_step = 0);   // a loop from a source motion: prompt b enters at starts[b] (null: first_step)
 
 // qkv_attn.hip: in_proj GEMM + self-attention of the denoiser's sa_block in one launch (f16x3 mode, S-format in / out)
 int launch_qkv_attention(const float* x, const float* w, const float* bias, const float* text_kv, const float* tables,

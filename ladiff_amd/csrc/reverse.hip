@@ -21,6 +21,8 @@ struct Call {
     bool pipeline;                        // this call runs the persistent pipeline kernel
     std::vector<unsigned char> plan;      // its block descriptors
     int plan_mr, plan_nb;
+    bool edit() const { return a.z0 != nullptr; }                // a loop from a source motion (ladiff_diffusion_reverse_from)
+    int first() const { return a.z0 != nullptr ? a.first_step : 0; }      // the first schedule position this call runs
 };
 
 // the generator of a call with per-prompt seeds: no seed of its own, the arrays by pointer
@@ -37,12 +39,15 @@ int prologue(const Call& c, hipStream_t st) {
     const ReverseWs& r = c.r;
     if (a.n_text > 1) LADIFF_TRY(denoiser_text_cache(c.W, a.text_emb, c.B2, r.tables, a.n_steps, r.cache, r.fwd, r.fwd_floats, st, a.n_text));
     else LADIFF_TRY(denoiser_text_static(c.W, a.text_emb, c.B2, r.cache, r.fwd, r.fwd_floats, st));      // the c table: per window, below
-    if (a.draw_init_noise && a.init_noise == nullptr)      // a tensor still wins over the generator
+    if (c.edit())                                          // source latents noised to each prompt's start; the step counter starts at first_step
+        LADIFF_TRY(launch_init_latents_from(a.z0, a.init_noise, a.init_noise == nullptr ? prompt_gen(a) : NoiseGen{0u, 0u, 0u, 0}, a.counts, a.coef,
+                                            a.starts, a.first_step, r.latents, a.B, a.T, r.d_step, st));
+    else if (a.draw_init_noise && a.init_noise == nullptr)      // a tensor still wins over the generator
         LADIFF_TRY(launch_init_latents_gen(prompt_gen(a), a.counts, a.init_noise_sigma, r.latents, a.B, a.T, st));
     else LADIFF_TRY(launch_init_latents(a.init_noise, a.counts, a.init_noise_sigma, r.latents, a.B, a.T, st));
     // [0] step index, [1] tail-kernel ticket, [2] window base.  A KERNEL, not hipMemsetAsync: this runs inside the captured prologue
     // graph, and a memset NODE is what an older exec replayed wrongly (see g_graph_epoch)
-    LADIFF_TRY(launch_zero_fill(reinterpret_cast<float*>(r.d_step), 4, st));
+    if (!c.edit()) LADIFF_TRY(launch_zero_fill(reinterpret_cast<float*>(r.d_step), 4, st));
     // One step = the nine denoiser layers + ONE tail launch (final LayerNorm of the guidance branches, guidance,
     // scheduler step, next step's network input, step counter).  The network input / last-layer output buffer of the
     // forward workspace is primed here.
@@ -55,7 +60,7 @@ int one_step(const Call& c, hipStream_t st) {
     LADIFF_TRY(denoiser_forward(c.W, c.WSp, r.tables, r.d_step, r.cache, r.window, r.latents, a.B, c.dup, a.T, a.counts, r.eps, r.fwd,
                                 r.fwd_floats, st, 0, c.B2, 1, a.n_text, r.d_step + 2));
     return launch_step_tail(c.xio, c.xios, c.W.norm.g, c.W.norm.b, r.latents, a.coef, r.d_step, a.step_noise, c.W.query_pe,
-                            a.guidance_scale, a.cfg, a.B, a.T, st, c.gen, a.guidance_scales, a.x0_prev);
+                            a.guidance_scale, a.cfg, a.B, a.T, st, c.gen, a.guidance_scales, a.x0_prev, c.edit(), a.starts, a.first_step);
 }
 
 // c-table rows of the window that starts at step `lo` (plain launches, outside the graphs: `lo` changes per window)
@@ -100,8 +105,10 @@ int ensure_graphs(Sampler* sp, const Call& c) {
         LADIFF_HIP(hipStreamSynchronize(c.s));
     } else {
         // several steps per graph launch (the step index lives in device memory): fewer ~9 us replay gaps
+        // (a loop that starts at first_step replays from there: the unroll divides the steps of its first, partial window too - first_step
+        // is part of this form's key)
         int unroll = 1;
-        for (int u = 2; u <= 10; ++u) if (c.r.window % u == 0) unroll = u;
+        for (int u = 2; u <= 10; ++u) if (c.r.window % u == 0 && c.first() % u == 0) unroll = u;
         sp->unroll = unroll;
         LADIFF_TRY(capture_graph(cs, [&](hipStream_t st) {
             int rc = 0;
@@ -129,21 +136,27 @@ int run_windows(Sampler* sp, const Call& c) {
     const ReverseWs& r = c.r;
     sp->last_pipeline = c.pipeline ? 1 : 0;
     sp->n_windows = 0;
-    for (int lo = 0; lo < a.n_steps; lo += r.window) {
+    // a loop from a source motion starts inside window first / window: that window is partial (positions from.. of it), the windows
+    // before it are not opened, and every table keeps its full-schedule index
+    const int first = c.first(), lo0 = first / r.window * r.window;
+    for (int lo = lo0; lo < a.n_steps; lo += r.window) {
+        const int from = lo < first ? first : lo, n = lo + r.window - from;
         LADIFF_TRY(open_window(c, lo));
-        if (lo == 0) LADIFF_HIP(hipEventRecord(sp->ev0, c.s));       // the loop itself: from the first step's first launch
-        const int wi = lo / r.window;
+        if (lo == lo0) LADIFF_HIP(hipEventRecord(sp->ev0, c.s));     // the loop itself: from the first step's first launch
+        const int wi = (lo - lo0) / r.window;
         if (sp->time_windows) {
             while ((int)sp->wev.size() < 2 * (wi + 1)) { hipEvent_t e; LADIFF_HIP(hipEventCreate(&e)); sp->wev.push_back(e); }
             LADIFF_HIP(hipEventRecord(sp->wev[2 * wi], c.s));
         }
         if (c.pipeline) {
-            LADIFF_TRY(launch_systolic_loop(c.W, r.sys, r.tables, den_cache_tkv(r.cache, c.B2, 1), den_cache_ctab(r.cache, c.B2, 1), r.window,
-                                            a.coef, a.step_noise, r.latents, a.counts, a.guidance_scale, a.B, a.T, lo, r.window, c.WSp ? 0 : 1,
+            // the c table's row of local step s of the launch is row from - lo + s of the window's
+            const float* ctab = den_cache_ctab(r.cache, c.B2, 1) + (size_t)(from - lo) * (c.B2 + 1) * LADIFF_LATENT_DIM;
+            LADIFF_TRY(launch_systolic_loop(c.W, r.sys, r.tables, den_cache_tkv(r.cache, c.B2, 1), ctab, r.window,
+                                            a.coef, a.step_noise, r.latents, a.counts, a.guidance_scale, a.B, a.T, from, n, c.WSp ? 0 : 1,
                                             c.plan_mr, c.plan_nb, c.s, a.cfg, sp->fault_wg, sp->timeout_ticks, c.gen, a.guidance_scales,
-                                            a.x0_prev));
+                                            a.x0_prev, c.edit(), a.starts, a.first_step));
         } else {
-            for (int i = 0; i < r.window / sp->unroll; ++i) LADIFF_HIP(hipGraphLaunch(sp->exec, c.s));
+            for (int i = 0; i < n / sp->unroll; ++i) LADIFF_HIP(hipGraphLaunch(sp->exec, c.s));
         }
         if (sp->time_windows) { LADIFF_HIP(hipEventRecord(sp->wev[2 * wi + 1], c.s)); sp->n_windows = wi + 1; }
     }
@@ -181,8 +194,8 @@ int diffusion_reverse(Sampler* sp, const DenoiserW& W, const DenoiserW* WSp, con
     if (!a.reuse_time_tables) LADIFF_TRY(denoiser_time_tables(W, a.sinusoid, a.n_steps, c.r.tables, c.r.fwd, c.r.fwd_floats, c.s));
     if (sp == nullptr) {
         LADIFF_TRY(prologue(c, c.s));
-        for (int i = 0; i < a.n_steps; ++i) {
-            if (i % c.r.window == 0) LADIFF_TRY(open_window(c, i));
+        for (int i = c.first(); i < a.n_steps; ++i) {
+            if (i % c.r.window == 0 || i == c.first()) LADIFF_TRY(open_window(c, i / c.r.window * c.r.window));
             LADIFF_TRY(one_step(c, c.s));
         }
     } else {

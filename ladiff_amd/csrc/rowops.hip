@@ -561,16 +561,23 @@ int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s) {
 // Classifier-free guidance + one scheduler step (ladiff.py:487-492), elementwise on [B,T,256].
 // x0p (multistep form, or null): the previous step's data prediction, addressed like lat.  It is read only at a step whose row has
 // k_m != 0 (step-uniform, like the noise branch) and this step's x0 is left in it; null = the one-step rule, column 6 is not read.
+// ED (a loop from a source motion, step_gate in step_rule.h): prompt b enters at starts[b], or at first_step without the array.  A template
+// flag: the kernel without it is exactly the code it was.
+template <bool ED>
 __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ lat,
                                                        const float* __restrict__ coef, const int32_t* __restrict__ d_step,
                                                        const float* __restrict__ noise, float g, const float* __restrict__ gs,
-                                                       int cfg, int T, size_t n4, const NoiseGen gen, float* __restrict__ x0p) {
+                                                       int cfg, int T, size_t n4, const NoiseGen gen, float* __restrict__ x0p,
+                                                       const int32_t* __restrict__ starts, int first_step) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
     const int step = *d_step;
     const int row = (int)(i / (D / 4));                                  // row = b * T + t
     if (gs != nullptr) g = gs[row / T];                                  // the prompt's own scale (launch-uniform branch)
-    const StepCoef c = step_coef(coef, step, x0p != nullptr);
+    StepCoef c = step_coef(coef, step, x0p != nullptr);
+    if constexpr (ED) {
+        if (!step_gate(c, step, starts != nullptr ? starts[row / T] : first_step)) return;      // frozen: nothing of the row is touched
+    }
     f32x4 e = ld4(eps + i * 4);
     if (cfg) e = guide4(e, ld4(eps + (n4 + i) * 4), g);
     f32x4 x = ld4(lat + i * 4);
@@ -580,10 +587,11 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     st4(lat + i * 4, x);
 }
 int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs, float* x0_prev) {
+                    float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs, float* x0_prev, bool edit,
+                    const int32_t* starts, int first_step) {
     const size_t n4 = (size_t)B * T * D / 4;
-    hipLaunchKernelGGL(cfg_step_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, coef, d_step, noise, g, gs, cfg, T, n4,
-                       gen, x0_prev);
+    hipLaunchKernelGGL(edit ? cfg_step_kernel<true> : cfg_step_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, coef,
+                       d_step, noise, g, gs, cfg, T, n4, gen, x0_prev, starts, first_step);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }
@@ -594,18 +602,22 @@ int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32
 // step's network input x = cat([latents]*2) + query_pos.pe (ladiff.py:472-474, ladiff_denoiser.py:251) written in place
 // over the last layer's output (fp32 + optional S-format twin).  The last workgroup to finish bumps the step counter
 // (every workgroup has read it before taking its ticket), so the whole tail of a step is one launch instead of five.
+// ED: as for cfg_step_kernel; a frozen row still gets the next network input latent + pe (the network runs on every row of the launch).
+template <bool ED>
 __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, float* __restrict__ xs, const float* __restrict__ ng,
                                                         const float* __restrict__ nb, float* __restrict__ lat,
                                                         const float* __restrict__ coef, int32_t* __restrict__ d_step,
                                                         const float* __restrict__ noise, const float* __restrict__ pe, float g,
                                                         const float* __restrict__ gs, int cfg, int B, int T, const NoiseGen gen,
-                                                        float* __restrict__ x0p) {
+                                                        float* __restrict__ x0p, const int32_t* __restrict__ starts, int first_step) {
     const int step = d_step[0];
     const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);      // row = b * T + t of the B prompts
     const int c = (threadIdx.x & 63) * 4;
     const int M = B * T;
     if (row < M) {
-        const StepCoef cf = step_coef(coef, step, x0p != nullptr);
+        StepCoef cf = step_coef(coef, step, x0p != nullptr);
+        bool live = true;                                                  // ED: the prompt has entered the schedule (step_gate)
+        if constexpr (ED) live = step_gate(cf, step, starts != nullptr ? starts[row / T] : first_step);
         if (gs != nullptr) g = gs[row / T];                                // the prompt's own scale (launch-uniform branch)
         const f32x4 gg = ld4(ng + c), bb = ld4(nb + c);
         f32x4 eu = ld4(x + (size_t)row * D + c), ec = eu;
@@ -624,25 +636,27 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
         const f32x4 p = ld4(pe + (size_t)(row % T) * D + c);
         // multistep form (x0p set, cfg_step_kernel): the previous data prediction of the row, only where this step's k_m uses it
         f32x4 m0, m1 = {0.f, 0.f, 0.f, 0.f};
-        if (cf.km != 0.f) m1 = ld4(x0p + (size_t)row * D + c);
+        if (cf.km != 0.f && live) m1 = ld4(x0p + (size_t)row * D + c);
         f32x4 xn;
+        if (live) {                          // a frozen row (ED) keeps its latents and leaves x0_prev alone
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {        // guide4 + step_rule4 (step_rule.h) written out: DESIGN 8g says why this launch keeps its own copy
-            const float e = cfg ? eu[i] + g * (ec[i] - eu[i]) : eu[i];
-            const float x0 = (l[i] - cf.sb * e) / cf.sa;
-            m0[i] = x0;
-            l[i] = cf.kx0 * x0 + cf.kx * l[i] + cf.ke * e + cf.kn * z[i];
-        }
-        if (x0p != nullptr) {
-            if (cf.km != 0.f) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) l[i] += cf.km * m1[i];
+            for (int i = 0; i < 4; ++i) {    // guide4 + step_rule4 (step_rule.h) written out: DESIGN 8g says why this launch keeps its own copy
+                const float e = cfg ? eu[i] + g * (ec[i] - eu[i]) : eu[i];
+                const float x0 = (l[i] - cf.sb * e) / cf.sa;
+                m0[i] = x0;
+                l[i] = cf.kx0 * x0 + cf.kx * l[i] + cf.ke * e + cf.kn * z[i];
             }
-            st4(x0p + (size_t)row * D + c, m0);
+            if (x0p != nullptr) {
+                if (cf.km != 0.f) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) l[i] += cf.km * m1[i];
+                }
+                st4(x0p + (size_t)row * D + c, m0);
+            }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) xn[i] = l[i] + p[i];
-        st4(lat + (size_t)row * D + c, l);
+        if (live) st4(lat + (size_t)row * D + c, l);
         st4(x + (size_t)row * D + c, xn);
         if (cfg) st4(x + (size_t)(M + row) * D + c, xn);
         if (xs != nullptr) {
@@ -658,10 +672,10 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
 }
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
                      const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs,
-                     float* x0_prev) {
+                     float* x0_prev, bool edit, const int32_t* starts, int first_step) {
     const int M = B * T;
-    hipLaunchKernelGGL(step_tail_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, x, xs, ng, nb, lat, coef,
-                       d_step, noise, pe, g, gs, cfg, B, T, gen, x0_prev);
+    hipLaunchKernelGGL(edit ? step_tail_kernel<true> : step_tail_kernel<false>, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s,
+                       x, xs, ng, nb, lat, coef, d_step, noise, pe, g, gs, cfg, B, T, gen, x0_prev, starts, first_step);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }
@@ -738,6 +752,47 @@ __global__ __launch_bounds__(256) void init_latents_gen_kernel(const NoiseGen ge
 int launch_init_latents_gen(const NoiseGen& gen, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s) {
     const int M = B * T;
     hipLaunchKernelGGL(init_latents_gen_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, gen, counts, sigma, T, M, lat);
+    LADIFF_LAUNCH_CHECK();
+    return 0;
+}
+
+// A loop from a source motion: latents[b,t] = valid * (alpha(s_b) z0[t,b] + sigma(s_b) noise[b,t]) with (alpha, sigma) = columns 0, 1 of
+// coefficient row s_b = starts[b] (or first_step without the array) - scheduler.add_noise(z0, noise, timesteps[s_b]).  z0 is [T,B,256], the
+// layout of the loop's result; noise = the tensor, or with a null tensor the generator at position -1 (gen.seeds set).  Thread 0 also
+// leaves the step counter at first_step (d_step null: the unit entry has none).
+__global__ __launch_bounds__(256) void init_latents_from_kernel(const float* __restrict__ z0, const float* __restrict__ noise, const NoiseGen gen,
+                                                                const int32_t* __restrict__ counts, const float* __restrict__ coef,
+                                                                const int32_t* __restrict__ starts, int first_step, int B, int T, int M,
+                                                                float* __restrict__ lat, int32_t* __restrict__ d_step) {
+    if (d_step != nullptr && blockIdx.x == 0 && threadIdx.x < 4) d_step[threadIdx.x] = threadIdx.x == 0 ? first_step : 0;
+    const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const int c = (threadIdx.x & 63) * 4;
+    if (row >= M) return;
+    const int b = row / T, t = row % T;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (counts == nullptr || t < counts[b]) {
+        const float* cf = coef + (size_t)(starts != nullptr ? starts[b] : first_step) * LADIFF_COEF_STRIDE;
+        const float alpha = cf[COEF_ALPHA_S], sigma = cf[COEF_SIGMA_S];
+        const f32x4 src = ld4(z0 + ((size_t)t * B + b) * D + c);
+        f32x4 n;
+        if (noise != nullptr) n = ld4(noise + (size_t)row * D + c);
+        else {
+            float z[4];
+            unsigned prompt;
+            const NoiseGen pg = noise_of_prompt(gen, b, prompt);
+            noise_normal4(pg, NOISE_INIT_POSITION, prompt, t, c / 4, z);
+            n = f32x4{z[0], z[1], z[2], z[3]};
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = alpha * src[i] + sigma * n[i];
+    }
+    st4(lat + (size_t)row * D + c, v);
+}
+int launch_init_latents_from(const float* z0, const float* noise, const NoiseGen& gen, const int32_t* counts, const float* coef,
+                             const int32_t* starts, int first_step, float* lat, int B, int T, int32_t* d_step, hipStream_t s) {
+    const int M = B * T;
+    hipLaunchKernelGGL(init_latents_from_kernel, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, z0, noise, gen, counts, coef,
+                       starts, first_step, B, T, M, lat, d_step);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }

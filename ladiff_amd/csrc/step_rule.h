@@ -35,6 +35,15 @@ __device__ __forceinline__ f32x4 step_noise4(const NoiseGen& gen, const float* n
     return f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// A loop from a source motion (ladiff_diffusion_reverse_from): prompt b enters the schedule at position `start`.  Returns whether the
+// prompt's rows take the step at `step` at all - false = frozen: the latent row keeps its bits, x0_prev is neither read nor written - and
+// makes the step AT `start` first order in the multistep form: k_x0 + k_m stands in for k_x0 (A (1 + 1/(2 r0)) - A/(2 r0) = A) and m1 is
+// not read.  Only coefficients change here, never the statements of step_rule4.  DESIGN 8h.
+__device__ __forceinline__ bool step_gate(StepCoef& c, int step, int start) {
+    if (step == start) { c.kx0 = c.kx0 + c.km; c.km = 0.f; }
+    return step >= start;
+}
+
 // x <- the step's result, returns this step's data prediction x0.  The one-step rule is ONE statement and `x += k_m m1` one of its own: an
 // addend more would re-associate what the compiler contracts.  m1 points to the previous prediction of these columns and is read only
 // inside the k_m != 0 branch (the first step finds anything there; in the one-step form the pointer means nothing).  DESIGN 8f, 8g.

@@ -123,6 +123,8 @@ struct SysArgs {
     int pause_mask, pause_len;            // stage types (R::PAUSE_BIT) that rest pause_len x ~60 ns between two polls of rows that are not there yet
     unsigned long long* stamps;           // diagnostic twin build only (-DLADIFF_STAMPS): [workgroup][step][block][8] realtime ticks
     float* x0p;                           // multistep form: the previous step's data prediction, addressed like lat; null: the one-step rule (last: the other fields keep their kernarg offsets)
+    const int32_t* starts;                // a loop from a source motion (the ED instantiations): [B] schedule position at which each prompt enters, or null: all at first_step
+    int first_step;
 };
 
 // In-kernel timeline (diagnostic twin build; the shipped library executes no stamp): s_memrealtime is one 100 MHz counter
@@ -1915,13 +1917,16 @@ struct SkipRole {
 // blocks hold one branch (16-row tiles).  Tail workgroup k owns the units u = k (mod NTAIL).
 // MS: the multistep form (SysArgs::x0p set).  A template flag and not a branch on the pointer: the one-step instantiations are then
 // exactly the code they were (a runtime branch cost the shipped 16-row instantiation a spill slot: the kernel sits at its register limit).
-template <int MR, int WS, int HO, bool MS = false>
+// ED: a loop from a source motion (SysArgs::starts / first_step, step_gate in step_rule.h).  The pair's start travels like its scale (Pay::st,
+// loaded in `issue`, applied in `compute`); a frozen pair still stores latent + pe with the next step's parity for both branches, so the
+// hand-off sees no difference.  A template flag for the reason MS is one: see the register table of DESIGN 8h.
+template <int MR, int WS, int HO, bool MS = false, bool ED = false>
 struct TailRole {
     static constexpr int RT = 16 * MR, NW = 4 * WS, NQ = 16 / NW;        // (prompt, latent) pairs per wave: <= 16 per unit
     struct Geo { int lat[NQ], t[NQ], rc[NQ], pad[NQ]; };                // latent row, position, conditional-branch row of pair q; padding row of a slot without a pair
     // gs: the guidance scale of the pair's own prompt; m1: the pair's previous data prediction (multistep form), loaded only at a
     // step whose k_m is not zero - it travels beside lt: read in `issue`, its successor written in `compute` of the same unit
-    struct Pay { f32x4 eu[NQ], ec[NQ], lt[NQ], zz[NQ], pe[NQ]; float gs[NQ]; f32x4 m1[MS ? NQ : 1]; };
+    struct Pay { f32x4 eu[NQ], ec[NQ], lt[NQ], zz[NQ], pe[NQ]; float gs[NQ]; f32x4 m1[MS ? NQ : 1]; int st[ED ? NQ : 1]; };
     const SysArgs& p; const Stage& st;
     f32x4 gg, bb;
     __amdgpu_buffer_rsrc_t rin, rout;
@@ -1992,7 +1997,8 @@ struct TailRole {
             const int q = wave + NW * i;
             y.zz[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (g.lat[i] >= 0) {
-                if constexpr (MS) { if (cf.km != 0.f) y.m1[i] = ld4(p.x0p + (size_t)g.lat[i] * D + c); }
+                if constexpr (ED) y.st[i] = p.starts != nullptr ? p.starts[g.lat[i] / T] : p.first_step;
+                if constexpr (MS) { if (cf.km != 0.f && (!ED || step > y.st[i])) y.m1[i] = ld4(p.x0p + (size_t)g.lat[i] * D + c); }
                 y.eu[i] = ld_sc1(rin, bu + q * 1024 + c * 4);
                 y.ec[i] = ld_sc1(rin, bc + g.rc[i] * 1024 + c * 4);
                 y.lt[i] = ld4(p.lat + (size_t)g.lat[i] * D + c);
@@ -2024,11 +2030,25 @@ struct TailRole {
                 row_stats4(ec, mean, rstd);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) ec[k] = (ec[k] - mean) * rstd * gg[k] + bb[k];
-                const f32x4 m0 = step_rule4(l, guide4(eu, ec, y.gs[i]), y.zz[i], reinterpret_cast<const float*>(&y.m1[MS ? i : 0]), cf);     // read only where `issue` loaded it
-                if constexpr (MS) st4(p.x0p + (size_t)g.lat[i] * D + c, m0);
+                // ED: before its own start the pair is frozen - the rule below still runs on its registers (the same statements in the
+                // same order as without ED: which products fuse must not depend on the flag) and a select drops the result; AT its
+                // start the multistep form is first order (step_gate)
+                StepCoef ci = cf;
+                bool live = true;
+                const f32x4 kept = l;
+                if constexpr (ED) {
+                    live = p.step_lo + s >= y.st[i];
+                    if constexpr (MS) (void)step_gate(ci, p.step_lo + s, y.st[i]);
+                }
+                const f32x4 m0 = step_rule4(l, guide4(eu, ec, y.gs[i]), y.zz[i], reinterpret_cast<const float*>(&y.m1[MS ? i : 0]), ci);     // read only where `issue` loaded it
+                if constexpr (ED) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) l[k] = live ? l[k] : kept[k];
+                }
+                if constexpr (MS) { if (live) st4(p.x0p + (size_t)g.lat[i] * D + c, m0); }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) xn[k] = l[k] + y.pe[i][k];
-                st4(p.lat + (size_t)g.lat[i] * D + c, l);
+                if (live) st4(p.lat + (size_t)g.lat[i] * D + c, l);
                 const unsigned par = HO ? (unsigned)((s + 1) & TAG_MASK) : 0u;     // the input of the NEXT local step
                 st_out<HO>(st, rout, bu + q * 1024 + c * 4, xn, par);          // after the last step nobody reads it
                 st_out<HO>(st, rout, bc + g.rc[i] * 1024 + c * 4, xn, par);
@@ -2045,10 +2065,10 @@ struct TailRole {
 // blocks, and a unit's latents are read in `issue` and written in `compute` of the SAME unit one step earlier - with other
 // units in between, so a prefetch never overtakes the update it depends on as long as a tail owns more than one unit; with
 // one unit it does not prefetch.  The multistep form's x0_prev rows follow the same rule: read in `issue` (Pay::m1), written in `compute`.
-template <int MR, int WS, bool MS>
-__device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, TailRole<MR, WS, 0, MS>& r, Ctl* ctl) {
-    typename TailRole<MR, WS, 0, MS>::Pay cur, nxt;
-    typename TailRole<MR, WS, 0, MS>::Geo gcur, gnxt;
+template <int MR, int WS, bool MS, bool ED>
+__device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, TailRole<MR, WS, 0, MS, ED>& r, Ctl* ctl) {
+    typename TailRole<MR, WS, 0, MS, ED>::Pay cur, nxt;
+    typename TailRole<MR, WS, 0, MS, ED>::Geo gcur, gnxt;
     bool have = false;
     const int lane = threadIdx.x & 63, u0 = st.slice;
     const int nu = p.split ? p.NB / 2 : p.NB;
@@ -2059,7 +2079,7 @@ __device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, Tai
         return (const gu32*)flag_of(p, st.wait_group, b, 0) + (lane < st.wait_n ? lane : lane - st.wait_n) * FLAG_STRIDE;
     };
     r.prime(nu);
-    typename TailRole<MR, WS, 0, MS>::Geo gnn;
+    typename TailRole<MR, WS, 0, MS, ED>::Geo gnn;
     if (u0 < nu) { r.geo(u0, gcur); r.geo(u0 + NTAIL < nu ? u0 + NTAIL : u0, gnxt); gnn = gnxt; }
     for (int s = 0; s < p.n_steps; ++s)
         for (int u = u0; u < nu; u += NTAIL) {
@@ -2110,10 +2130,10 @@ __device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, Tai
 
 // Tagged hand-off: no barrier and no flag - every wave owns the (prompt, latent) pairs `wave + NW i` of its units, settles on the
 // two rows of each pair, updates the latents and stores the next step's input rows with the next step's parity.
-template <int MR, int WS, int HO, bool MS>
-__device__ __forceinline__ void tail_loop_tag(const SysArgs& p, const Stage& st, TailRole<MR, WS, HO, MS>& r) {
-    typename TailRole<MR, WS, HO, MS>::Pay cur;
-    typename TailRole<MR, WS, HO, MS>::Geo gcur, gnxt, gnn;
+template <int MR, int WS, int HO, bool MS, bool ED>
+__device__ __forceinline__ void tail_loop_tag(const SysArgs& p, const Stage& st, TailRole<MR, WS, HO, MS, ED>& r) {
+    typename TailRole<MR, WS, HO, MS, ED>::Pay cur;
+    typename TailRole<MR, WS, HO, MS, ED>::Geo gcur, gnxt, gnn;
     const int u0 = st.slice;
     const int nu = p.split ? p.NB / 2 : p.NB;
     r.prime(nu);
@@ -2154,7 +2174,8 @@ __device__ __forceinline__ void tail_loop_tag(const SysArgs& p, const Stage& st,
 // EQ = QKV's loader waves request the next block's rows early (QkvRole::split_loop<true>): the instantiation for launches in which rows
 // queue up (SysArgs::look_ahead); a kernel of its own, so that the other launches run exactly the code without it
 // MS = the TAIL stage runs the multistep form of the scheduler step (TailRole; SysArgs::x0p is set): kernels of their own as well
-template <int MR, int AR, int WS, int HO, bool EQ = false, bool MS = false>
+// ED = the TAIL stage gates every pair by its prompt's start (a loop from a source motion; SysArgs::starts / first_step): likewise
+template <int MR, int AR, int WS, int HO, bool EQ = false, bool MS = false, bool ED = false>
 __global__ __launch_bounds__(256 * WS, 1) void systolic_loop_kernel(const SysArgs p) {
     static_assert(WS == 1 || MR == 1, "two waves per SIMD: 16-row blocks only (the reduce parts' slot tables hold 12 slots: wave + 8 q needs q < 1)");
     // all LDS is dynamic (a static variable would shift the dynamic base off its 16-byte alignment, cdna_hip_programming.md G17)
@@ -2244,7 +2265,7 @@ __global__ __launch_bounds__(256 * WS, 1) void systolic_loop_kernel(const SysArg
         case R_SKIP: with_ho([&](auto hc) { SkipRole<MR, AR, WS, decltype(hc)::value> r(p, st, lds); run(r); }); break;
         case R_TAIL:
             with_ho([&](auto hc) {
-                TailRole<MR, WS, decltype(hc)::value, MS> r(p, st, lds);
+                TailRole<MR, WS, decltype(hc)::value, MS, ED> r(p, st, lds);
                 if constexpr (HO) tail_loop_tag(p, st, r);
                 else tail_loop(p, st, r, ctl);
             });
@@ -2319,9 +2340,10 @@ constexpr int LOOK_AHEAD_BLOCKS = 72;      // see `settle`: 58 blocks (128 promp
 
 namespace {
 // Every instantiation of the kernel, once: the launch opts each into its dynamic LDS and selects by the same rows.
-struct LoopKernel { int fp32, MR, waves, tagged; bool look_ahead; void (*fn)(const SysArgs); int threads; bool multistep; };
-#define LOOP_KERNEL(AR, MR, WS, HO, EQ) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ>, 256 * WS, false}
-#define LOOP_KERNEL_MS(AR, MR, WS, HO, EQ) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ, true>, 256 * WS, true}
+struct LoopKernel { int fp32, MR, waves, tagged; bool look_ahead; void (*fn)(const SysArgs); int threads; bool multistep, edit; };
+#define LOOP_KERNEL(AR, MR, WS, HO, EQ) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ>, 256 * WS, false, false}
+#define LOOP_KERNEL_MS(AR, MR, WS, HO, EQ) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ, true>, 256 * WS, true, false}
+#define LOOP_KERNEL_ED(AR, MR, WS, HO, EQ, MS) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ, MS, true>, 256 * WS, MS, true}
 const LoopKernel LOOP_KERNELS[] = {
     // flags: 16-row blocks with two waves per SIMD (ladiff_debug_set_handoff(0)) and 32-row blocks, split | fp32
     LOOP_KERNEL(0, 1, 2, 0, false), LOOP_KERNEL(0, 2, 1, 0, false), LOOP_KERNEL(1, 1, 2, 0, false), LOOP_KERNEL(1, 2, 1, 0, false),
@@ -2332,9 +2354,15 @@ const LoopKernel LOOP_KERNELS[] = {
     // forms behind the measurement switches (16-row blocks with flags, one wave per SIMD) have none: LADIFF_ERR_UNSUPPORTED
     LOOP_KERNEL_MS(0, 2, 1, 0, false), LOOP_KERNEL_MS(1, 2, 1, 0, false), LOOP_KERNEL_MS(0, 1, 2, 1, false), LOOP_KERNEL_MS(1, 1, 2, 1, false),
     LOOP_KERNEL_MS(0, 1, 2, 1, true), LOOP_KERNEL_MS(1, 1, 2, 1, true),
+    // a loop from a source motion (z0 set): the same shipped plans, one-step and multistep
+    LOOP_KERNEL_ED(0, 2, 1, 0, false, false), LOOP_KERNEL_ED(1, 2, 1, 0, false, false), LOOP_KERNEL_ED(0, 1, 2, 1, false, false),
+    LOOP_KERNEL_ED(1, 1, 2, 1, false, false), LOOP_KERNEL_ED(0, 1, 2, 1, true, false), LOOP_KERNEL_ED(1, 1, 2, 1, true, false),
+    LOOP_KERNEL_ED(0, 2, 1, 0, false, true), LOOP_KERNEL_ED(1, 2, 1, 0, false, true), LOOP_KERNEL_ED(0, 1, 2, 1, false, true),
+    LOOP_KERNEL_ED(1, 1, 2, 1, false, true), LOOP_KERNEL_ED(0, 1, 2, 1, true, true), LOOP_KERNEL_ED(1, 1, 2, 1, true, true),
 };
 #undef LOOP_KERNEL
 #undef LOOP_KERNEL_MS
+#undef LOOP_KERNEL_ED
 }  // namespace
 
 int sys_reset_status(float* ws, hipStream_t s) {
@@ -2346,7 +2374,7 @@ int sys_reset_status(float* ws, hipStream_t s) {
 int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab,
                          const float* coef, const float* noise, float* lat, const int32_t* counts, float gscale, int B, int T,
                          int step_lo, int n, int fp32, int MR, int NB, hipStream_t s, int cfg, int fault_wg, unsigned long long timeout_ticks,
-                         const NoiseGen& gen, const float* gscales, float* x0_prev) {
+                         const NoiseGen& gen, const float* gscales, float* x0_prev, bool edit, const int32_t* starts, int first_step) {
     // fault_wg / timeout_ticks: the caller's SAMPLER's fault injection (ladiff_sampler_set_fault; -1 / 0 = none / default bound)
     const SysLayout L = sys_layout(MR, NB);
     SysArgs a;
@@ -2355,7 +2383,7 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     a.flags = reinterpret_cast<unsigned*>(ws + L.off_flags);
     a.status = reinterpret_cast<unsigned*>(ws + L.off_status);
     a.tables = tables; a.tkv = tkv; a.ctab = ctab; a.coef = coef; a.noise = noise; a.pe = W.query_pe; a.ng = W.norm.g; a.nb = W.norm.b;
-    a.lat = lat; a.x0p = x0_prev; a.counts = counts; a.gscale = gscale; a.gscales = gscales; a.B = B; a.B2 = cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
+    a.lat = lat; a.x0p = x0_prev; a.starts = starts; a.first_step = first_step; a.counts = counts; a.gscale = gscale; a.gscales = gscales; a.B = B; a.B2 = cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
     a.n_ctab = n_ctab;
     a.split = cfg ? L.split : 0;       // no guidance: every block is a unit of its own (sys_pack_blocks)
     a.force_mismatch = g_xcd_local == 2 ? 1 : 0;
@@ -2414,7 +2442,7 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     const LoopKernel* k = nullptr;
     for (const LoopKernel& c : LOOP_KERNELS)
         if (c.fp32 == (fp32 ? 1 : 0) && c.MR == mr && c.waves == waves && c.tagged == (tagged ? 1 : 0) && c.look_ahead == la &&
-            c.multistep == (x0_prev != nullptr))
+            c.multistep == (x0_prev != nullptr) && c.edit == edit)
             k = &c;
     if (k == nullptr) return LADIFF_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k->fn, dim3(L.nwg), dim3(k->threads), SYS_LDS_BYTES, s, a);

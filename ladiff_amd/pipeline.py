@@ -313,6 +313,9 @@ class LADIFF(nn.Module):
             "gscales": torch.empty(B, dtype=torch.float32, device=dev),
             "seeds": torch.empty(B, dtype=torch.int64, device=dev),
             "pindex": torch.empty(B, dtype=torch.int32, device=dev),
+            # an edit's source latents [T,B,256] and per-prompt start positions (ladiff_diffusion_reverse_from): by pointer as well
+            "z0": torch.empty(T, B, 256, dtype=torch.float32, device=dev),
+            "starts": torch.empty(B, dtype=torch.int32, device=dev),
             # per-step noise (DDPM / eta > 0): the CALLER's tensor is used in place when it is a contiguous fp32 tensor on this device
             # (1000 steps x 128 prompts are 655 MB: not held twice, not copied per call); otherwise a plan-owned copy, made on first need
             "step_noise": None,
@@ -433,8 +436,28 @@ class LADIFF(nn.Module):
             raise ValueError("per-prompt guidance scales need a model built with classifier-free guidance (guidance_scale > 1)")
         return per
 
+    def _start_steps(self, B, strength, start_steps):
+        """The per-prompt start positions of an edit as a list of B ints, checked on the host (the loop takes them as device data):
+        from `strength` (one number or B of them, `scheduler.start_step`) or from `start_steps` (B positions)."""
+        n = int(self.num_inference_timesteps)
+        if (strength is None) == (start_steps is None):
+            raise ValueError("source_latents need exactly one of strength and start_steps")
+        if start_steps is not None:
+            starts = [int(s) for s in (start_steps.tolist() if torch.is_tensor(start_steps) else start_steps)]
+        else:
+            if torch.is_tensor(strength):
+                strength = strength.tolist()
+            values = list(strength) if hasattr(strength, "__len__") else [strength] * B
+            starts = [self.scheduler.start_step(v, n) for v in values]
+        if len(starts) != B:
+            raise ValueError(f"{len(starts)} start positions for {B} prompts")
+        if any(s < 0 or s >= n for s in starts):
+            raise ValueError(f"start positions {starts} outside a schedule of {n} steps")
+        return starts
+
     def _diffusion_reverse(self, encoder_hidden_states, lengths=None, init_noise=None, step_noise=None, noise_seed=None, *,
-                           guidance_scale=None, seeds=None, prompt_index=None):
+                           guidance_scale=None, seeds=None, prompt_index=None, source_latents=None, strength=None, start_steps=None,
+                           first_step=None):
         """text_emb [2B,1,768] (unconditional half first), lengths list[int] -> z [max_it, B, 256]  (ladiff.py:333-571).
         Stochastic schedules (DDPM, eta > 0): `step_noise` [n,B,T,256] if given; otherwise the noise is drawn on the device where it
         is consumed (csrc/noise_gen.h) from `noise_seed` (default: a seed taken from torch's CPU generator, so torch.manual_seed makes
@@ -448,8 +471,31 @@ class LADIFF(nn.Module):
           of (`noise_seed`, `noise_first_prompt` + b) - the same (seed, index) gives the same motion whatever the rest of the batch is,
           however it is chunked or sharded.  With `seeds` and no `init_noise` the initial noise is drawn on the device too (schedule
           position -1 of the same generator) and torch's generators are not touched.
-        The values travel in per-plan device buffers: new values do not capture the graphs again."""
+        The values travel in per-plan device buffers: new values do not capture the graphs again.
+
+        An edit (SDEdit): `source_latents` [T,B,256] (the layout of this method's result and of `vae.encode`'s) are noised
+        to each prompt's own schedule position and denoised from there.  `strength` (one number or B of them; `scheduler.start_step`)
+        or `start_steps` (B positions) says where; the loop runs positions min(starts) .. n - 1 and a prompt that starts later keeps its
+        latents until then.  `init_noise` (or the prompts' keys at position -1) is the noise that is added; `init_noise_sigma` is not.
+        `first_step` (optional) is the first position the launches run instead of min(starts) - it must not exceed it; given alone,
+        without strength or start_steps, every prompt starts there and the loop takes no array."""
         dev = encoder_hidden_states.device
+        starts = None
+        if source_latents is not None:
+            n_sched = int(self.num_inference_timesteps)
+            if first_step is not None and not 0 <= int(first_step) < n_sched:
+                raise ValueError(f"first_step {first_step} outside a schedule of {n_sched} steps")
+            if first_step is None or strength is not None or start_steps is not None:
+                starts = self._start_steps(len(lengths), strength, start_steps)
+                if first_step is not None and int(first_step) > min(starts):
+                    raise ValueError(f"first_step {first_step} is past the earliest start {min(starts)}")
+            if int(encoder_hidden_states.shape[1]) != 1:
+                raise NotImplementedError("an edit with a text sequence (n_text > 1) is not built")
+            want = (self._counts(lengths)[0] if self.test_efficiency else self.max_it, len(lengths), 256)
+            if tuple(source_latents.shape) != want:
+                raise ValueError(f"source_latents {tuple(source_latents.shape)}: expected [T,B,256] = {want}, the layout of the loop's result")
+        elif strength is not None or start_steps is not None or first_step is not None:
+            raise ValueError("strength / start_steps / first_step need source_latents")
         per = {}
         if guidance_scale is not None or seeds is not None or prompt_index is not None:
             per = self._prompt_params(len(lengths), guidance_scale, seeds, prompt_index)     # argument errors first: host work only
@@ -477,7 +523,8 @@ class LADIFF(nn.Module):
         self.last_noise_seed = None if step_noise is not None or noise_seed is None else int(noise_seed)
         first = int(self.noise_first_prompt)
         if len(spans) == 1:
-            return self._reverse_one(encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed, first, per)
+            return self._reverse_one(encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed, first, per,
+                                     source_latents, starts, first_step)
         # prompts are independent (attention is per sample, guidance pairs the two branches of one prompt): a large batch is
         # several launches of the loop on contiguous prompt ranges, the noise drawn for the whole batch and sliced
         if init_noise is None and seeds is None:
@@ -488,10 +535,13 @@ class LADIFF(nn.Module):
             part = {k: (v[lo:hi] if torch.is_tensor(v) else v) for k, v in per.items()}      # a caller's prompt_index is not shifted
             zs.append(self._reverse_one(text[:, lo:hi].reshape(dup * (hi - lo), n_text, 768), lengths[lo:hi], counts[lo:hi], T,
                                         None if init_noise is None else init_noise[lo:hi],
-                                        None if step_noise is None else step_noise[:, lo:hi], noise_seed, first + lo, part))
+                                        None if step_noise is None else step_noise[:, lo:hi], noise_seed, first + lo, part,
+                                        None if source_latents is None else source_latents[:, lo:hi], None if starts is None else starts[lo:hi],
+                                        first_step))
         return torch.cat(zs, dim=1)
 
-    def _reverse_one(self, encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed=None, first_prompt=0, per=None):
+    def _reverse_one(self, encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed=None, first_prompt=0, per=None,
+                     source=None, starts=None, first_step=None):
         """One launch sequence of the loop on B prompts: prologue graph, N steps (pipeline kernel or step graphs), final masking."""
         L = _lib.lib()
         dev = encoder_hidden_states.device
@@ -503,6 +553,13 @@ class LADIFF(nn.Module):
         plan = self._get_plan(B, T, self.num_inference_timesteps, self.eta, dev, n_text)
         self._last.append(plan)
         n, need_noise = plan["n"], plan["need_noise"]
+        if source is not None and max(starts if starts is not None else [first_step]) >= n:
+            raise ValueError(f"start positions {starts if starts is not None else first_step} outside the schedule's {n} steps")
+        if source is None:
+            first_step = 0
+        elif first_step is None:
+            first_step = min(starts)                                  # the launch runs positions first_step .. n - 1
+        first_step = int(first_step)
         sampler = plan["sampler"]
         if self._stream is None or self._stream.device != dev:
             self._stream = torch.cuda.Stream(device=dev)
@@ -544,6 +601,10 @@ class LADIFF(nn.Module):
             x0_prev = plan.get("x0_prev")
             entry = L.ladiff_diffusion_reverse_prompts if x0_prev is None else L.ladiff_diffusion_reverse_multistep
             tail = (run.cuda_stream,) if x0_prev is None else (_lib.ptr(x0_prev), run.cuda_stream)
+            if source is not None:                                    # an edit: every loop form, the fallback's re-run included
+                entry = L.ladiff_diffusion_reverse_from
+                tail = (None if x0_prev is None else _lib.ptr(x0_prev), _lib.ptr(plan["z0"]), None if starts is None else plan["starts"].data_ptr(), first_step,
+                        run.cuda_stream)
             _lib.check(entry(
                 sampler, wt.array,
                 wt.split_array() if _lib.is_split(self.precision) else None, wt.generation, _lib.ptr(plan["text"]),
@@ -575,6 +636,10 @@ class LADIFF(nn.Module):
             for name, values in (("gscales", gscales), ("seeds", seeds), ("pindex", pindex)):
                 if values is not None:
                     plan[name].copy_(values, non_blocking=True)
+            if source is not None:
+                plan["z0"].copy_(source, non_blocking=True)
+                if starts is not None:
+                    plan["starts"].copy_(_lib.device_ints(starts, dev))
             plan["counts"].copy_(_lib.device_ints(counts, dev))       # device-to-device: the graph bakes plan["counts"] in
             if noise_t is not None and noise_t is not step_noise:
                 noise_t.copy_(step_noise)
@@ -664,13 +729,16 @@ class LADIFF(nn.Module):
 
     # ------------------------------------------------------------------ callers' surface
     def sample(self, text_emb, lengths, init_noise=None, step_noise=None, check=True, noise_seed=None, *, guidance_scale=None, seeds=None,
-               prompt_index=None):
+               prompt_index=None, source_latents=None, strength=None, start_steps=None):
         """text embeddings -> (z [max_it,B,256], feats [B,max(len),nfeats]): ladiff.py:266 + :283.  Returns checked frames: the
         decode is queued, then the host waits for the loop's status words (LadiffHipError if the loop was abandoned).
         check=False skips the wait (the host may then queue a call ahead) - the caller owes a `check()` before using the frames.
-        guidance_scale / seeds / prompt_index: one value per prompt, see `_diffusion_reverse`."""
+        guidance_scale / seeds / prompt_index: one value per prompt, see `_diffusion_reverse`.
+        source_latents with strength or start_steps: an edit of those latents instead of a sample from noise, see there."""
+        edit = {} if source_latents is None and strength is None and start_steps is None else \
+            {"source_latents": source_latents, "strength": strength, "start_steps": start_steps}
         z = self._diffusion_reverse(text_emb, lengths, init_noise=init_noise, step_noise=step_noise, noise_seed=noise_seed,
-                                    guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index)
+                                    guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index, **edit)
         feats = self.vae.decode(z, lengths)
         if check:
             self.check()
@@ -714,6 +782,43 @@ class LADIFF(nn.Module):
         self.times.append(time.time() - start)
         joints = self.feats2joints(feats_rst.detach().cpu())
         return remove_padding(joints, lengths)
+
+    def edit(self, batch, strength, *, latents=None, guidance_scale=None, seeds=None, prompt_index=None, eps=None):
+        """Text-guided edit of a motion (SDEdit): the source is encoded, noised to the schedule position of `strength` (one number or one
+        per prompt, `scheduler.start_step`) and denoised from there under `batch["text"]`.  `batch["length"]` are the TARGET lengths (the
+        valid mask of the loop and of the decode); the source is `batch["motion"]` (features as `recon_from_motion` takes them, of
+        `batch["source_length"]` frames, default the target's) through `vae.encode` - its sample, drawn as `recon_from_motion` draws it, or
+        with `eps` - or `latents=` [T,B,256], e.g. the z of an earlier `sample`.  Rows of the source past its own latent count are zeros,
+        as `encode` leaves them.  Returns what `forward` returns."""
+        texts, lengths = batch["text"], [int(l) for l in batch["length"]]
+        if self.text_encoder is None or (self.feats2joints is None and self.feats2joints_device is None):
+            raise RuntimeError("LADIFF.edit needs a text_encoder callable and datamodule.feats2joints")
+        if (latents is None) == (batch.get("motion") is None):
+            raise ValueError('LADIFF.edit takes exactly one source: batch["motion"] or latents=')
+        starts = self._start_steps(len(lengths), strength, None)         # argument errors before any GPU work
+        self._check_loaded_weights()
+        start = time.time()
+        with torch.no_grad():
+            if latents is None:
+                src_len = [int(l) for l in batch.get("source_length", lengths)]
+                latents, _, _ = self.vae.encode(batch["motion"].detach().to(self.device), src_len, **({} if eps is None else {"eps": eps}))
+            text_emb = self.text_encoder(self._guided_texts(texts))
+            z = self._diffusion_reverse(text_emb, lengths, guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index,
+                                        source_latents=latents.to(self.device, torch.float32), start_steps=starts)
+            feats_rst = self.vae.decode(z, lengths)
+        f2j = self.feats2joints_device or (lambda f: self.feats2joints(f.detach().cpu()))
+        joints = f2j(feats_rst.detach())
+        torch.cuda.synchronize()
+        self.check()
+        self.times.append(time.time() - start)
+        return remove_padding(joints.cpu(), lengths)
+
+    demo_strength = None      # `forward_motion_style_transfer`: the strength of the demo's edit (a loop owner sets it from its config), default 0.6
+
+    def forward_motion_style_transfer(self, batch):
+        """The name the reference's demo.py:182 calls (its own LADIFF class has no such method).  Here: `edit` of `batch["motion"]`
+        under `batch["text"]` - SDEdit, not MLD's three-branch guidance."""
+        return self.edit(batch, strength=self.demo_strength or 0.6)
 
     def _guided_texts(self, texts):
         """`[""] * B + texts` when classifier-free guidance is on, the texts alone otherwise (ladiff.py:258-264, :1039-1047, :1135-1142)."""

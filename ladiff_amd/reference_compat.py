@@ -8,7 +8,9 @@ already imported: a finder at the front of `sys.meta_path` serves later imports,
 
     python -m ladiff_amd.reference_compat demo.py --cfg ... --example ...
 
-runs a script of the reference unchanged, in this process, after `install()`.
+runs a script of the reference unchanged, in this process, after `install()`.  `demo.py:182` then finds
+`LADIFF.forward_motion_style_transfer(batch)`, which the reference's own class lacks: here it is `LADIFF.edit(batch, strength=
+model.demo_strength or 0.6)` - SDEdit, not MLD's three-branch guidance.
 """
 import importlib.abc
 import importlib.util

@@ -108,6 +108,19 @@ class _Scheduler:
             a = a.unsqueeze(-1)
         return a ** 0.5 * original_samples + (1 - a) ** 0.5 * noise
 
+    @staticmethod
+    def start_step(strength, n_steps):
+        """The schedule position at which an edit of this `strength` enters a schedule of `n_steps` positions (diffusers' img2img
+        rule: `n - min(int(n * strength), n)`): strength 1 starts from pure noise at position 0, a small strength runs the last few
+        positions only.  `LADIFF.edit` noises the source latents to this position and denoises from there."""
+        strength, n_steps = float(strength), int(n_steps)
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"strength {strength} is not in (0, 1]")
+        start = n_steps - min(int(n_steps * strength), n_steps)
+        if n_steps < 1 or start >= n_steps:
+            raise ValueError(f"strength {strength} leaves no step of a schedule of {n_steps}")
+        return start
+
     def __len__(self):
         return self.config.num_train_timesteps
 
