@@ -201,26 +201,28 @@ int ladiff_linear_cross_attention(const float* const* w, int layer, const float*
 }
 
 // ------------------------------------------------------------------ guidance + scheduler
+// the step end of the three entries below: no generator and no per-prompt scales
+static StepEnd step_end(const float* coef, const float* step_noise, float guidance_scale, int cfg, float* x0_prev, bool edit, const int32_t* starts, int first_step) {
+    return StepEnd{coef, step_noise, NoiseGen{0u, 0u, 0u, 0}, guidance_scale, nullptr, cfg, x0_prev, edit, starts, first_step};
+}
 int ladiff_cfg_scheduler_step(const float* eps, float* latents, const float* coef, const int32_t* d_step,
                               const float* step_noise, float guidance_scale, int cfg, int B, int T,
                               ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(eps && latents && coef && d_step && B > 0 && T > 0);
-    return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream));
+    return launch_cfg_step(eps, latents, d_step, step_end(coef, step_noise, guidance_scale, cfg, nullptr, false, nullptr, 0), B, T, S(stream));
 }
 int ladiff_cfg_scheduler_step_multistep(const float* eps, float* latents, float* x0_prev, const float* coef, const int32_t* d_step,
                                         const float* step_noise, float guidance_scale, int cfg, int B, int T, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(eps && latents && x0_prev && coef && d_step && B > 0 && T > 0);
     if (reinterpret_cast<uintptr_t>(x0_prev) & 15) return LADIFF_ERR_SHAPE;
-    return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream), NoiseGen{0u, 0u, 0u, 0}, nullptr,
-                           x0_prev);
+    return launch_cfg_step(eps, latents, d_step, step_end(coef, step_noise, guidance_scale, cfg, x0_prev, false, nullptr, 0), B, T, S(stream));
 }
 int ladiff_cfg_scheduler_step_from(const float* eps, float* latents, float* x0_prev, const float* coef, const int32_t* d_step,
                                    const float* step_noise, float guidance_scale, int cfg, int B, int T, const int32_t* starts, int first_step,
                                    ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(eps && latents && coef && d_step && B > 0 && T > 0 && first_step >= 0);
     if ((reinterpret_cast<uintptr_t>(x0_prev) & 15) || (reinterpret_cast<uintptr_t>(starts) & 3)) return LADIFF_ERR_SHAPE;
-    return launch_cfg_step(eps, latents, coef, d_step, step_noise, guidance_scale, cfg, B, T, S(stream), NoiseGen{0u, 0u, 0u, 0}, nullptr,
-                           x0_prev, true, starts, first_step);
+    return launch_cfg_step(eps, latents, d_step, step_end(coef, step_noise, guidance_scale, cfg, x0_prev, true, starts, first_step), B, T, S(stream));
 }
 int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(d_step);
@@ -281,13 +283,13 @@ int ladiff_reverse_plan(int B, int T, const int32_t* h_counts, int masked, int l
 
 int ladiff_debug_set_stage_waves(int waves_per_simd) {
     LADIFF_CHECK_ARG(waves_per_simd == 1 || waves_per_simd == 2);
-    g_waves16 = waves_per_simd;
+    g_loop.waves16 = waves_per_simd;
     return 0;
 }
 
 int ladiff_debug_set_handoff(int tagged) {
     LADIFF_CHECK_ARG(tagged == 0 || tagged == 1);
-    g_handoff = tagged;
+    g_loop.handoff = tagged;
     return 0;
 }
 
@@ -297,49 +299,49 @@ int ladiff_debug_set_mlp_variant(int v) {
 #else
     LADIFF_CHECK_ARG(v >= 0 && v <= 3);          // workgroup forms of the fused feed-forward kernel; every one gives the same result
 #endif
-    g_mlp_variant = v;
+    g_dec.mlp_variant = v;
     return 0;
 }
 
 int ladiff_debug_set_decoder_fusion(int on) {
     LADIFF_CHECK_ARG(on >= 0 && on <= 126 && (on & 3) != 3 && (on & 48) != 48);
-    g_dec_out_cross = (on & 64) ? 0 : 1;
-    g_dec_fused_mlp = on & 3;
-    g_dec_small_rows_path = (on & 4) ? 0 : 1;
-    g_dec_final_split = (on & 8) ? 0 : 1;
-    g_dec_fused_attn = (on & 16) ? 0 : (on & 32) ? 2 : 1;
+    g_dec.out_cross = (on & 64) ? 0 : 1;
+    g_dec.fused_mlp = on & 3;
+    g_dec.small_rows_path = (on & 4) ? 0 : 1;
+    g_dec.final_split = (on & 8) ? 0 : 1;
+    g_dec.fused_attn = (on & 16) ? 0 : (on & 32) ? 2 : 1;
     return 0;
 }
 
 int ladiff_debug_set_stage_plan(int v) {
     LADIFF_CHECK_ARG(v >= 0 && v <= 1);
-    g_stage_plan = v;
+    g_loop.stage_plan = v;
     return 0;
 }
 
 int ladiff_debug_set_poll_pause(int mask, int len) {
     LADIFF_CHECK_ARG(mask >= 0 && mask <= 255 && len >= 0 && len <= 64);
-    g_poll_pause = mask | (len << 8);
+    g_loop.poll_pause = mask | (len << 8);
     return 0;
 }
 
 int ladiff_debug_set_pacing(int eighths, int mask) {
-    if (eighths == -1) { g_pace = -1; return 0; }       // back to the built-in choice by launch size
+    if (eighths == -1) { g_loop.pace = -1; return 0; }       // back to the built-in choice by launch size
     LADIFF_CHECK_ARG(eighths >= 0 && eighths <= 8 && mask >= 0 && mask <= 255);
-    g_pace = eighths | (mask << 8);
+    g_loop.pace = eighths | (mask << 8);
     return 0;
 }
 
 int ladiff_debug_set_stage_delay(int mask, int len) {
     LADIFF_CHECK_ARG(mask >= -1 && mask <= 255 && len >= 0 && len <= 64);
-    g_stage_delay = mask < 0 ? -1 : (mask | (len << 8));
+    g_loop.stage_delay = mask < 0 ? -1 : (mask | (len << 8));
     return 0;
 }
 
 int ladiff_debug_set_loop_thresholds(int look_ahead_from, int small_upto) {
     LADIFF_CHECK_ARG(look_ahead_from >= -1 && small_upto >= -1);
-    g_look_ahead_from = look_ahead_from;
-    g_small_upto = small_upto;
+    g_loop.look_ahead_from = look_ahead_from;
+    g_loop.small_upto = small_upto;
     return 0;
 }
 
@@ -353,7 +355,7 @@ int ladiff_debug_graph_instantiations(void) { return g_graph_instantiations.load
 
 int ladiff_debug_set_xcd_local(int on) {
     LADIFF_CHECK_ARG(on >= 0 && on <= 2);
-    g_xcd_local = on;
+    g_loop.xcd_local = on;
     return 0;
 }
 
@@ -458,7 +460,7 @@ int ladiff_mlp_ln_fused(const float* xs, const float* x, const float* w1s, const
                         int M, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(xs && x && w1s && b1 && w2s && b2 && ln_gamma && ln_beta && (y || ys) && M >= 0);
     if ((ln2_gamma == nullptr) != (ln2_beta == nullptr)) return LADIFF_ERR_ARG;
-    return launch_dec_mlp(xs, x, w1s, b1, w2s, b2, ln_gamma, ln_beta, ln2_gamma, ln2_beta, y, ys, M, S(stream));
+    return launch_dec_mlp(xs, x, w1s, b1, w2s, b2, ln_gamma, ln_beta, ln2_gamma, ln2_beta, y, ys, M, S(stream), g_dec.mlp_variant.load());
 }
 
 int ladiff_split_rows(const float* x, float* y, int R, int K, ladiff_stream_t stream) {
@@ -764,7 +766,7 @@ int ladiff_vae_decode(const float* const* w, const float* const* w_split, const 
     LADIFF_CHECK_ARG(load_weights(W, w) && z && lengths && feats && ws && B >= 0);
     if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
     return vae_decode(W, w_split ? &WS : nullptr, z, lengths, counts, nullptr, 0, B, F, T, C, feats, (float*)ws, ws_bytes / sizeof(float),
-                      S(stream));
+                      S(stream), g_dec.snapshot());
 }
 
 // ---- the decode as a replayed hipGraph (launch-bound sizes: config c1's 8 x 60 frames is ~110 launches of a few microseconds)
@@ -801,8 +803,9 @@ int ladiff_vae_decode_graphed(void* graph, const float* const* w, const float* c
     if (F < 1 || F > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;      // as the ragged entry
     if (ws_bytes < ladiff_decoder_workspace_bytes(B, F, T, C)) return LADIFF_ERR_WORKSPACE;
     hipStream_t s = S(stream);
+    const DecSwitches sw = g_dec.snapshot();      // one reading: what the key holds is what the capture runs
     const GraphKey key = decode_key(w, w_split, DEC_NPARAMS, weights_generation, z, lengths, counts, row_off, total_rows, B, F, T, C, feats, ws,
-                                    stream, g_dec_fused_mlp, g_dec_small_rows_path, g_dec_final_split, g_mlp_variant, g_dec_fused_attn);
+                                    stream, sw);
     if (!(dg->exec && dg->slot.key == key && dg->slot.newest())) {
         if (dg->exec) { LADIFF_HIP(hipStreamSynchronize(s)); (void)hipGraphExecDestroy(dg->exec); dg->exec = nullptr; }
         LADIFF_TRY(dec_mlp_prepare());            // kernel attributes are set outside the capture
@@ -813,7 +816,7 @@ int ladiff_vae_decode_graphed(void* graph, const float* const* w, const float* c
             // inside the capture: a zero-fill KERNEL, never a memset node (g_graph_epoch)
             if (row_off != nullptr) LADIFF_TRY(launch_zero_fill(feats, (size_t)B * F * C, cs));
             return vae_decode(W, w_split ? &WS : nullptr, z, lengths, counts, row_off, total_rows, B, F, T, C, feats, (float*)ws,
-                              ws_bytes / sizeof(float), cs);
+                              ws_bytes / sizeof(float), cs, sw);
         }, &dg->exec));
         dg->slot.stamp(key);
     }
@@ -833,7 +836,7 @@ int ladiff_vae_decode_ragged(const float* const* w, const float* const* w_split,
     // frames past each length: zero, whatever the buffer held (ladiff_vae.py:356-360)
     LADIFF_HIP(hipMemsetAsync(feats, 0, (size_t)B * F * C * sizeof(float), S(stream)));
     return vae_decode(W, w_split ? &WS : nullptr, z, lengths, counts, row_off, total_rows, B, F, T, C, feats, (float*)ws,
-                      ws_bytes / sizeof(float), S(stream));
+                      ws_bytes / sizeof(float), S(stream), g_dec.snapshot());
 }
 
 }  // extern "C"

@@ -381,8 +381,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void dec_mlp_kernel(const MlpArgs 
     }
 }
 
-std::atomic<int> g_mlp_variant{0};   // measurement switch (ladiff_debug_set_mlp_variant)
-
 // hipFuncSetAttribute is per DEVICE and must not land inside a stream capture: once per device, under a mutex; the graphed decode
 // calls it before it begins its capture
 int dec_mlp_prepare() {
@@ -414,14 +412,14 @@ int dec_mlp_min_rows() { return 10000; }
 
 // y / ys [M,256] = LN3(x + lin2(gelu(lin1(x)))) (then LN4 when g4 != NULL); xs = S-format twin of x, w1 / w2 S-format
 int launch_dec_mlp(const float* xs, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3,
-                   const float* be3, const float* g4, const float* be4, float* y, float* ys, int M, hipStream_t s) {
+                   const float* be3, const float* g4, const float* be4, float* y, float* ys, int M, hipStream_t s, int variant) {
     if (M <= 0) return 0;
     LADIFF_TRY(dec_mlp_prepare());
     MlpArgs a{xs, x, w1, b1, w2, b2, g3, be3, g4, be4, y, ys, M};
     // every workgroup streams all 2 MB of weights: 128-row workgroups when they fill the chip, 64-row ones (twice as many) otherwise
     // (measured, profiles/r3: 25088 rows 111 us <4,2> / 116 <8,1> / 137 <4,1>; 12544 rows 106 / 108 / 71; the caller keeps the
     // three-launch form below dec_mlp_min_rows())
-    int form = g_mlp_variant;                      // 0: by size, 1: <8, 1>, 2: <4, 1>, 3: <4, 2>
+    int form = variant;                            // 0: by size, 1: <8, 1>, 2: <4, 1>, 3: <4, 2>
     if (form >= 21) form = 0;                      // 21 .. 23: timing builds of the attention kernel (dec_qkv_attn.hip)
     // round 6: with one batch per wave behind vmcnt(0) the two-waves-per-SIMD form is the fastest at 25088 rows (decode 1.92 ms against
     // 2.02 with <4, 2>; round 5's counted-wait ring: 2.00 / 1.97) - a wave's LDS-DMA issue falls under its SIMD partner's MFMAs

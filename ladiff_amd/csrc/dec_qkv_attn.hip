@@ -546,7 +546,7 @@ int launch_dec_qkv_attn(const float* xs, const float* w, const float* bias, cons
                         reinterpret_cast<const void*>(dec_qkv_attn_kernel<2>), reinterpret_cast<const void*>(dec_qkv_attn_kernel<3>),
                         reinterpret_cast<const void*>(dec_qkv_attn_kernel<4>), reinterpret_cast<const void*>(dec_qkv_attn_kernel<5>),
                         reinterpret_cast<const void*>(dec_qkv_attn_kernel<6>)};
-    const int v = g_mlp_variant;
+    const int v = g_dec.mlp_variant.load();
     kern = k[v >= 21 && v <= 26 ? v - 20 : 0];
 #endif
     LADIFF_HIP(hipLaunchKernel(kern, dim3(8 * H * ((B + 7) / 8)), dim3(512), args, QA_LDS, s));

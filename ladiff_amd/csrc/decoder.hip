@@ -17,11 +17,7 @@ namespace ladiff {
 #endif
 
 constexpr int DEC_SMALL_ROWS = 4096;
-std::atomic<int> g_dec_out_cross{1};          // measurement switch (+ 64): self-attention out_proj GEMM + cross-attention row kernel as two launches (the path before)
-std::atomic<int> g_dec_fused_attn{1};         // measurement switch (+ 16): in_proj GEMM + attention kernel as two launches (the path before)
-std::atomic<int> g_dec_final_split{1};        // measurement switch (ladiff_debug_set_decoder_fusion + 8): final_layer on the fp32 kernel as in round 2
-std::atomic<int> g_dec_small_rows_path{1};    // measurement switch (ladiff_debug_set_decoder_fusion bit 2 clear / set): the small-M GEMM routing
-std::atomic<int> g_dec_fused_mlp{1};          // measurement switch (ladiff_debug_set_decoder_fusion): 0 = linear1 / linear2 / LayerNorm as three launches, 1 = fused from dec_mlp_min_rows() rows, 2 = fused always
+DecSwitchAtoms g_dec;                          // the measurement switches (model.h); a decode runs on its caller's snapshot `sw`
 
 static GemmArgs lin(const float* A, int lda, const float* W, const float* bias, float* Y, int ldy, int M, int N, int K,
                     int act = ACT_NONE) {
@@ -37,7 +33,7 @@ static GemmArgs lin(const float* A, int lda, const float* W, const float* bias, 
 // frames are masked keys, cross_attention.py:367-371, and zeroed at the end, ladiff_vae.py:356-360), so a sample's frames come
 // out as in the padded layout; they are scattered to feats[b, f < length] of a [B, F, C] tensor the caller has zero-filled.
 int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int32_t* lengths, const int32_t* counts,
-               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s) {
+               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s, const DecSwitches& sw) {
     if (F < 1 || F > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;
     const bool ragged = row_off != nullptr;
     if (ragged && (R < 0 || (size_t)R > (size_t)B * F)) return LADIFF_ERR_SHAPE;
@@ -77,10 +73,10 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
     // GEMM whatever its size (profiles/r3: 40 of them were 0.63 of a 0.9 ms decode).  Below DEC_SMALL_ROWS the f16x3 path runs its
     // GEMMs on the denoiser's small-M kernels instead (gemm_kr.hip: K-resident 32 / 64 / 80-row tiles, K = 1024 as four partial planes
     // that the LayerNorm row pass sums) - the same S-format operands and products, 3 - 4x the workgroups.
-    const bool small = sp && M < DEC_SMALL_ROWS && g_dec_small_rows_path;
+    const bool small = sp && M < DEC_SMALL_ROWS && sw.small_rows_path;
     // in_proj inside the attention kernel (dec_qkv_attn.hip): from DEC_SMALL_ROWS frame rows up (8 x 60 frames: 0.47 ms against 0.45
     // with the small-M in_proj + attention launches; 128 x 196: 2.28 against 2.41, profiles/r3/15)
-    const bool fused_attn = sp && g_dec_fused_attn && (M >= DEC_SMALL_ROWS || g_dec_fused_attn == 2);
+    const bool fused_attn = sp && sw.fused_attn && (M >= DEC_SMALL_ROWS || sw.fused_attn == 2);
     auto krs = [&](const float* A, int K, const float* W, const float* bias, float* Y, float* Ys, int ldy, int N, int act,
                    const float* res, int rows) -> int {
         KrArgs g;
@@ -159,7 +155,7 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         // norm1: fused in the GEMM epilogue in fp32 mode; in f16x3 mode the GEMM writes x + out_proj(att) and the only reader of
         // norm1's output, the cross-attention kernel below, normalises its rows as it loads them (one row kernel pass less)
         const NormW* n1_late = nullptr;
-        if (sp && !small && g_dec_out_cross) {
+        if (sp && !small && sw.out_cross) {
             // f16x3 mode, many rows: out_proj + residual + norm1 + cross-attention + residual + norm2 in ONE kernel that keeps Wo in
             // its registers (dec_cross.hip): x + out_proj(att) is never written
             LADIFF_TRY(launch_decoder_out_cross(att, cur, Ls.self_attn.out_w, L.self_attn.out_b, L.norm1.g, L.norm1.b, L.cross_attn.out_b,
@@ -184,9 +180,9 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         // ---- feed-forward, GELU(erf), + residual + norm3 (+ decoder.norm on the last layer, cross_attention.py:150-151)   :410-412
         float* dst = is_in ? SK[l] : P[0];
         float* dsts = is_in ? SKs[l] : Ps[0];
-        if (sp && g_dec_fused_mlp && (M >= dec_mlp_min_rows() || g_dec_fused_mlp == 2)) {     // one kernel: the hidden rows never leave the registers (dec_mlp.hip)
+        if (sp && sw.fused_mlp && (M >= dec_mlp_min_rows() || sw.fused_mlp == 2)) {     // one kernel: the hidden rows never leave the registers (dec_mlp.hip)
             LADIFF_TRY(launch_dec_mlp(Ps[2], P[2], Ls.lin1.w, L.lin1.b, Ls.lin2.w, L.lin2.b, L.norm3.g, L.norm3.b,
-                                      last ? w.norm.g : nullptr, last ? w.norm.b : nullptr, dst, dsts, M, s)); DEC_CUT();
+                                      last ? w.norm.g : nullptr, last ? w.norm.b : nullptr, dst, dsts, M, s, sw.mlp_variant)); DEC_CUT();
         } else if (small) {
             LADIFF_TRY(krs(Ps[2], D, Ls.lin1.w, L.lin1.b, nullptr, hid, FF, FF, ACT_GELU, nullptr, M)); DEC_CUT();
             // linear2: K = 1024 as four partial planes (the q|k|v + attention buffers are free by now), summed by the LayerNorm pass
@@ -205,7 +201,7 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         cur = dst; curs = dsts;
     }
     // final_layer + zero padded frames, written as [B, F, C]   ladiff_vae.py:356-360
-    if (sp && M >= DEC_SMALL_ROWS && g_dec_final_split) {
+    if (sp && M >= DEC_SMALL_ROWS && sw.final_split) {
         // f16x3 mode: the projection runs on the large-M f16x3 kernel over whole 128-column tiles, into the (free) hidden buffer, and a
         // row kernel moves the C real columns into [B, F, C] (zeroing padded frames / scattering ragged rows): 94 us -> ~40 us at 25088
         // rows.  The tiles need Np = ceil(C / 128) 128 weight rows: the library pads the caller's C rows ITSELF (a 1-KiB-per-row copy

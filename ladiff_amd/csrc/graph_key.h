@@ -12,7 +12,7 @@
 namespace ladiff {
 
 struct GraphKey {
-    static constexpr int CAPACITY = 36;                  // entries; the sampler's key has 30, 31 with x0_prev, up to 34 with z0 / starts / first_step, the decode graph's 20.  One too many aborts.
+    static constexpr int CAPACITY = 36;                  // entries; the sampler's key has 30, 31 with x0_prev, up to 34 with z0 / starts / first_step, the decode graph's 21.  One too many aborts.
     uint64_t v[CAPACITY] = {0};
     int n = 0;
 
@@ -131,12 +131,18 @@ inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, i
     return k;
 }
 
-// Key of a decode graph (ladiff_vae_decode_graphed).  The five measurement switches change the launch sequence: part of the key.
-// (g_dec_out_cross changes it too and is NOT keyed: a known gap)
+struct DecSwitches {              // one reading of the decoder's measurement switches (model.h, g_dec): each changes a decode's launch sequence
+    int fused_mlp;                // ladiff_debug_set_decoder_fusion: 0 = linear1 / linear2 / LayerNorm as three launches, 1 = fused from dec_mlp_min_rows() rows, 2 = fused always
+    int small_rows_path;          // (bit 2 clear / set): the small-M GEMM routing
+    int final_split;              // (+ 8 clears it): final_layer on the large-M f16x3 kernel, else on the fp32 kernel as in round 2
+    int out_cross;                // (+ 64 clears it): out_proj + cross-attention in one kernel, else the GEMM + the row kernel as two launches (the path before)
+    int fused_attn;               // (+ 16 clears it, + 32 = always): in_proj inside the attention kernel, else GEMM + attention kernel as two launches (the path before)
+    int mlp_variant;              // ladiff_debug_set_mlp_variant: workgroup form of the fused feed-forward kernel
+};
+// Key of a decode graph (ladiff_vae_decode_graphed): EVERY field of the call's switch snapshot is part of it.
 inline GraphKey decode_key(const float* const* w, const float* const* w_split, int n_params, uint64_t weights_generation, const float* z,
                            const int32_t* lengths, const int32_t* counts, const int32_t* row_off, int total_rows, int B, int F, int T, int C,
-                           const float* feats, const void* ws, const void* stream, int dec_fused_mlp, int dec_small_rows_path,
-                           int dec_final_split, int mlp_variant, int dec_fused_attn) {
+                           const float* feats, const void* ws, const void* stream, const DecSwitches& sw) {
     GraphKey k;
     k.add(z);
     k.add(lengths);
@@ -151,11 +157,12 @@ inline GraphKey decode_key(const float* const* w, const float* const* w_split, i
     k.add(C);
     k.add(total_rows);
     k.add(w_split != nullptr ? 1 : 0);
-    k.add(dec_fused_mlp);
-    k.add(dec_small_rows_path);
-    k.add(dec_final_split);
-    k.add(mlp_variant);
-    k.add(dec_fused_attn);
+    k.add(sw.fused_mlp);
+    k.add(sw.small_rows_path);
+    k.add(sw.final_split);
+    k.add(sw.mlp_variant);
+    k.add(sw.fused_attn);
+    k.add(sw.out_cross);
     k.add(weights_hash(w, w_split, n_params));
     k.add(weights_generation);
     return k;

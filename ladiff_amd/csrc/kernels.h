@@ -51,15 +51,19 @@ int launch_pad_rows(const float* src, const float* srcb, float* dst, float* dstb
 int launch_zero_fill(float* x, size_t n, hipStream_t s);          // kernel, not a memset node (graphs: graph_cache.h g_graph_epoch)
 int launch_silu(const float* x, float* y, size_t n, hipStream_t s);
 int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s);
-int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
-                    const float* gs = nullptr, float* x0_prev = nullptr, bool edit = false, const int32_t* starts = nullptr,
-                    int first_step = 0);   // edit: prompt b enters the schedule at starts[b] (null: first_step), step_gate in step_rule.h; gs: [B] per-prompt scales (device) instead of g; x0_prev: [B,T,256] previous data prediction (multistep form), or null
+// What the end of a denoiser step takes besides its buffers and shape.  Whoever builds one sets every field: no defaults to hide a forgotten one.
+struct StepEnd {
+    const float *coef, *noise;    // the schedule's coefficient rows (step_coef, step_rule.h); step-noise tensor, or null: `gen`
+    NoiseGen gen;                 // stands in for `noise` (off: NoiseGen{0u, 0u, 0u, 0}); schedules without noise look at neither
+    float g; const float* gs;     // guidance scale of the call; [B] per-prompt scales (device) instead of it, or null
+    int cfg;                      // classifier-free guidance: the network ran on both branches
+    float* x0_prev;               // [B,T,256] previous data prediction (multistep form), or null (one-step rule)
+    bool edit; const int32_t* starts; int first_step;   // a loop from a source motion: prompt b enters the schedule at starts[b] ([B], device; null: at first_step), step_gate in step_rule.h
+};
+int launch_cfg_step(const float* eps, float* lat, const int32_t* d_step, const StepEnd& e, int B, int T, hipStream_t s);
 int launch_advance(int32_t* d_step, hipStream_t s);
-int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
-                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
-                     const float* gs = nullptr, float* x0_prev = nullptr, bool edit = false, const int32_t* starts = nullptr,
-                     int first_step = 0);            // as for launch_cfg_step
+int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, int32_t* d_step, const float* pe, const StepEnd& e,
+                     int B, int T, hipStream_t s);
 int launch_noise_fill(const NoiseGen& gen, int step0, int n, int B, int T, float* out, hipStream_t s);
 int launch_init_latents(const float* noise, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);
 int launch_init_latents_gen(const NoiseGen& gen, const int32_t* counts, float sigma, float* lat, int B, int T, hipStream_t s);   // gen.seeds set

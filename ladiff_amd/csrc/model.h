@@ -53,30 +53,23 @@ int launch_diffusion_losses(const float* pred, const float* noise, size_t n, dou
 struct Sampler;      // sampler.h
 int diffusion_reverse(Sampler* sp, const DenoiserW& w, const DenoiserW* w_split, const ReverseArgs& a);
 
-// Measurement switches (include/ladiff_hip.h, ladiff_debug_set_*): process-wide atomics.  Every value they accept selects a launch
-// form that the tests hold to the same tolerances; the timing builds that produce garbage exist in the diagnostic twin only
-// (-DLADIFF_STAMPS).
-extern std::atomic<int> g_dec_fused_mlp;
-extern std::atomic<int> g_dec_small_rows_path;
-extern std::atomic<int> g_dec_final_split;
-extern std::atomic<int> g_dec_out_cross;
-extern std::atomic<int> g_stage_plan;
-extern std::atomic<int> g_poll_pause;
-extern std::atomic<int> g_stage_delay;
-extern std::atomic<int> g_pace;
-extern std::atomic<int> g_look_ahead_from, g_small_upto;
-extern std::atomic<int> g_dec_fused_attn;
-extern std::atomic<int> g_mlp_variant;
+// decoder.hip.  Its measurement switches (ladiff_debug_set_decoder_fusion / _mlp_variant), an object like the loop's (systolic_plan.h, g_loop): a decode
+// reads them ONCE - the snapshot (DecSwitches, graph_key.h) routes the whole call and is in its graph's key
+struct DecSwitchAtoms {
+    std::atomic<int> fused_mlp{1}, small_rows_path{1}, final_split{1}, out_cross{1}, fused_attn{1}, mlp_variant{0};
+    DecSwitches snapshot() const { return {fused_mlp, small_rows_path, final_split, out_cross, fused_attn, mlp_variant}; }
+};
+extern DecSwitchAtoms g_dec;
 int dec_mlp_prepare();           // per-device kernel attributes (dynamic LDS): outside any stream capture, under a mutex
 int dec_qkv_attn_prepare();
 int dec_cross_prepare();
 int dec_mlp_min_rows();
 int vae_decode(const DecoderW& w, const DecoderW* w_split, const float* z, const int32_t* lengths, const int32_t* counts,
-               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s);
+               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s, const DecSwitches& sw);
 
 // dec_mlp.hip: the decoder layer's feed-forward block (linear1, GELU, linear2, residual, LayerNorm[s]) as one kernel, f16x3 mode
 int launch_dec_mlp(const float* xs, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3,
-                   const float* be3, const float* g4, const float* be4, float* y, float* ys, int M, hipStream_t s);
+                   const float* be3, const float* g4, const float* be4, float* y, float* ys, int M, hipStream_t s, int variant);      // DecSwitches::mlp_variant
 
 int vae_encode(const EncoderW& w, const EncoderW* w_split, const float* features, const int32_t* lengths,
                const int32_t* counts, const float* eps, int B, int F, int T, int C, float* mu, float* sd, float* latent, float* ws,
@@ -89,18 +82,11 @@ extern unsigned long long* g_sys_stamps;
 extern int g_sys_probe;
 #endif
 bool sys_supported(int B, int T, int cfg, bool split);
-extern std::atomic<int> g_waves16;
-extern std::atomic<int> g_handoff;
 int sys_reset_status(float* ws, hipStream_t s);
-extern std::atomic<int> g_xcd_local;
 int sys_build_stages(const DenoiserW& W, const DenoiserW& WS, float* ws, int MR, int NB, std::vector<unsigned char>& host);   // probes the device, then the planner's
-int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab,
-                         const float* coef, const float* noise, float* lat, const int32_t* counts, float gscale, int B, int T,
-                         int step_lo, int n, int fp32, int MR, int NB, hipStream_t s, int cfg = 1, int fault_wg = -1,
-                         unsigned long long timeout_ticks = 0, const NoiseGen& gen = NoiseGen{0u, 0u, 0u, 0},
-                         const float* gscales = nullptr,       // [B] per-prompt guidance scales (device) instead of gscale
-                         float* x0_prev = nullptr,             // [B,T,256] previous data prediction (multistep form), or null
-                         bool edit = false, const int32_t* starts = nullptr, int first_step = 0);   // a loop from a source motion: prompt b enters at starts[b] (null: first_step)
+int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab, float* lat,
+                         const int32_t* counts, const StepEnd& e, int B, int T, int step_lo, int n, int fp32, int MR, int NB, hipStream_t s,
+                         int fault_wg, unsigned long long timeout_ticks);
 
 // qkv_attn.hip: in_proj GEMM + self-attention of the denoiser's sa_block in one launch (f16x3 mode, S-format in / out)
 int launch_qkv_attention(const float* x, const float* w, const float* bias, const float* text_kv, const float* tables,

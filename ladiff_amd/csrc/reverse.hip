@@ -16,13 +16,13 @@ struct Call {
     ReverseWs r;
     hipStream_t s;                        // the caller's stream
     int dup, B2;                          // guidance: the network sees cat([latents]*2) with text [uncond | cond]  ladiff.py:472-474
-    NoiseGen gen;
+    StepEnd end;                          // what every step's tail takes, whichever loop form runs it
     float *xio, *xios;                    // network input / last-layer output buffer of the forward workspace
     bool pipeline;                        // this call runs the persistent pipeline kernel
     std::vector<unsigned char> plan;      // its block descriptors
     int plan_mr, plan_nb;
-    bool edit() const { return a.z0 != nullptr; }                // a loop from a source motion (ladiff_diffusion_reverse_from)
-    int first() const { return a.z0 != nullptr ? a.first_step : 0; }      // the first schedule position this call runs
+    bool edit() const { return end.edit; }                       // a loop from a source motion (ladiff_diffusion_reverse_from): z0 set
+    int first() const { return end.edit ? a.first_step : 0; }    // the first schedule position this call runs
 };
 
 // the generator of a call with per-prompt seeds: no seed of its own, the arrays by pointer
@@ -59,8 +59,7 @@ int one_step(const Call& c, hipStream_t st) {
     const ReverseWs& r = c.r;
     LADIFF_TRY(denoiser_forward(c.W, c.WSp, r.tables, r.d_step, r.cache, r.window, r.latents, a.B, c.dup, a.T, a.counts, r.eps, r.fwd,
                                 r.fwd_floats, st, 0, c.B2, 1, a.n_text, r.d_step + 2));
-    return launch_step_tail(c.xio, c.xios, c.W.norm.g, c.W.norm.b, r.latents, a.coef, r.d_step, a.step_noise, c.W.query_pe,
-                            a.guidance_scale, a.cfg, a.B, a.T, st, c.gen, a.guidance_scales, a.x0_prev, c.edit(), a.starts, a.first_step);
+    return launch_step_tail(c.xio, c.xios, c.W.norm.g, c.W.norm.b, r.latents, r.d_step, c.W.query_pe, c.end, a.B, a.T, st);
 }
 
 // c-table rows of the window that starts at step `lo` (plain launches, outside the graphs: `lo` changes per window)
@@ -74,7 +73,7 @@ int open_window(const Call& c, int lo) {
 // (c) The sampler's graphs (and, for the pipeline, the stage table in the workspace) are this call's: captured again when the key
 // differs, or when another handle of the library has instantiated since (GraphSlot::newest).
 int ensure_graphs(Sampler* sp, const Call& c) {
-    const unsigned noise[4] = {c.gen.seed_lo, c.gen.seed_hi, c.gen.prompt0, (unsigned)c.gen.on};
+    const unsigned noise[4] = {c.end.gen.seed_lo, c.end.gen.seed_hi, c.end.gen.prompt0, (unsigned)c.end.gen.on};
     const GraphKey key = sampler_key(c.a, DEN_NPARAMS, c.pipeline, c.plan_mr, c.plan_nb, noise);
     const bool same = sp->setup && sp->slot.key == key;
     if (same && sp->slot.newest()) return 0;
@@ -151,10 +150,8 @@ int run_windows(Sampler* sp, const Call& c) {
         if (c.pipeline) {
             // the c table's row of local step s of the launch is row from - lo + s of the window's
             const float* ctab = den_cache_ctab(r.cache, c.B2, 1) + (size_t)(from - lo) * (c.B2 + 1) * LADIFF_LATENT_DIM;
-            LADIFF_TRY(launch_systolic_loop(c.W, r.sys, r.tables, den_cache_tkv(r.cache, c.B2, 1), ctab, r.window,
-                                            a.coef, a.step_noise, r.latents, a.counts, a.guidance_scale, a.B, a.T, from, n, c.WSp ? 0 : 1,
-                                            c.plan_mr, c.plan_nb, c.s, a.cfg, sp->fault_wg, sp->timeout_ticks, c.gen, a.guidance_scales,
-                                            a.x0_prev, c.edit(), a.starts, a.first_step));
+            LADIFF_TRY(launch_systolic_loop(c.W, r.sys, r.tables, den_cache_tkv(r.cache, c.B2, 1), ctab, r.window, r.latents, a.counts, c.end,
+                                            a.B, a.T, from, n, c.WSp ? 0 : 1, c.plan_mr, c.plan_nb, c.s, sp->fault_wg, sp->timeout_ticks));
         } else {
             for (int i = 0; i < n / sp->unroll; ++i) LADIFF_HIP(hipGraphLaunch(sp->exec, c.s));
         }
@@ -168,16 +165,18 @@ int run_windows(Sampler* sp, const Call& c) {
 
 int diffusion_reverse(Sampler* sp, const DenoiserW& W, const DenoiserW* WSp, const ReverseArgs& a) {
     const int dup = a.cfg ? 2 : 1;
-    Call c{W, WSp, a, carve_reverse(a.ws, a.B, a.T, a.n_steps, a.n_text), reinterpret_cast<hipStream_t>(a.stream), dup, dup * a.B,
-           NoiseGen{0u, 0u, 0u, 0}, nullptr, nullptr, false, {}, 2, 0};
-    if (a.ws_bytes < c.r.total_bytes) return LADIFF_ERR_WORKSPACE;
     // the sampler's generator stands in for a step-noise tensor the caller did not pass (schedules without noise never look at either)
     // A generator that is off is all zeros: its seed must not be part of any graph key (the Python loop owner draws a fresh seed per call,
     // also for deterministic schedules - a key that changed with it re-captured ~150-node graphs on every launch-per-stage call).
-    if (sp != nullptr && a.step_noise == nullptr && sp->gen.on) c.gen = sp->gen;
+    NoiseGen gen{0u, 0u, 0u, 0};
+    if (sp != nullptr && a.step_noise == nullptr && sp->gen.on) gen = sp->gen;
     // per-prompt seeds need no handle to carry them (they are arguments of the call) and replace the sampler's seed: the words that
     // enter the key are then constants, the arrays are keyed by pointer
-    if (a.seeds != nullptr && a.step_noise == nullptr) c.gen = prompt_gen(a);
+    if (a.seeds != nullptr && a.step_noise == nullptr) gen = prompt_gen(a);
+    Call c{W, WSp, a, carve_reverse(a.ws, a.B, a.T, a.n_steps, a.n_text), reinterpret_cast<hipStream_t>(a.stream), dup, dup * a.B,
+           StepEnd{a.coef, a.step_noise, gen, a.guidance_scale, a.guidance_scales, a.cfg, a.x0_prev, a.z0 != nullptr, a.starts, a.first_step},
+           nullptr, nullptr, false, {}, 2, 0};
+    if (a.ws_bytes < c.r.total_bytes) return LADIFF_ERR_WORKSPACE;
     den_loop_io(c.r.fwd, c.B2 * a.T, &c.xio, &c.xios);
     if (WSp == nullptr) c.xios = nullptr;
     // without guidance the pipeline runs one-branch 16-row blocks, which need the latent counts on the host (or no masking at all)

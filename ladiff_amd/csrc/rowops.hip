@@ -586,12 +586,10 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     if (x0p != nullptr) st4(x0p + i * 4, m0);
     st4(lat + i * 4, x);
 }
-int launch_cfg_step(const float* eps, float* lat, const float* coef, const int32_t* d_step, const float* noise,
-                    float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs, float* x0_prev, bool edit,
-                    const int32_t* starts, int first_step) {
+int launch_cfg_step(const float* eps, float* lat, const int32_t* d_step, const StepEnd& e, int B, int T, hipStream_t s) {
     const size_t n4 = (size_t)B * T * D / 4;
-    hipLaunchKernelGGL(edit ? cfg_step_kernel<true> : cfg_step_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, coef,
-                       d_step, noise, g, gs, cfg, T, n4, gen, x0_prev, starts, first_step);
+    hipLaunchKernelGGL(e.edit ? cfg_step_kernel<true> : cfg_step_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat,
+                       e.coef, d_step, e.noise, e.g, e.gs, e.cfg, T, n4, e.gen, e.x0_prev, e.starts, e.first_step);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }
@@ -670,12 +668,11 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
         if (ticket == (int)gridDim.x - 1) { d_step[1] = 0; d_step[0] = step + 1; }
     }
 }
-int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, const float* coef, int32_t* d_step,
-                     const float* noise, const float* pe, float g, int cfg, int B, int T, hipStream_t s, const NoiseGen& gen, const float* gs,
-                     float* x0_prev, bool edit, const int32_t* starts, int first_step) {
+int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, int32_t* d_step, const float* pe, const StepEnd& e,
+                     int B, int T, hipStream_t s) {
     const int M = B * T;
-    hipLaunchKernelGGL(edit ? step_tail_kernel<true> : step_tail_kernel<false>, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s,
-                       x, xs, ng, nb, lat, coef, d_step, noise, pe, g, gs, cfg, B, T, gen, x0_prev, starts, first_step);
+    hipLaunchKernelGGL(e.edit ? step_tail_kernel<true> : step_tail_kernel<false>, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s,
+                       x, xs, ng, nb, lat, e.coef, d_step, e.noise, pe, e.g, e.gs, e.cfg, B, T, e.gen, e.x0_prev, e.starts, e.first_step);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }

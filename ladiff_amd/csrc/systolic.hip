@@ -44,8 +44,8 @@
 // launch-per-stage loop (8 hidden slices instead of 4 K-slices).
 //
 // This file: the device code (hand-off protocols, the eight roles, the kernel), the XCD probe and the launch.  The plan they run - the
-// constants, Stage, BlockDesc, the workspace carve, the block packing, the stage table and its placement - is host arithmetic with no HIP
-// call: systolic_plan.h / systolic_plan.hip, built and tested without a GPU (tests/planner_check.cpp).
+// constants, Stage, BlockDesc, the workspace carve, the block packing, the stage table and its placement - and the launch policy are host
+// arithmetic with no HIP call: systolic_plan.h / systolic_plan.hip, built and tested without a GPU (tests/planner_check.cpp).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -57,12 +57,6 @@
 #include "tile_mma.h"
 
 namespace ladiff {
-
-std::atomic<int> g_stage_plan{0};   // measurement switch: ladiff_debug_set_stage_plan (red_plan, systolic_plan.h)
-std::atomic<int> g_poll_pause{0};   // measurement switch: ladiff_debug_set_poll_pause (mask | len << 8)
-std::atomic<int> g_stage_delay{-1}; // ladiff_debug_set_stage_delay (mask | len << 8); -1: by block count (launch_systolic_loop)
-std::atomic<int> g_look_ahead_from{-1}, g_small_upto{-1};   // ladiff_debug_set_loop_thresholds (-1: the built-in block counts)
-std::atomic<int> g_pace{-1};   // ladiff_debug_set_pacing (eighths | mask << 8); -1: by block count - STYL sleeps half of its last observed wait before polling in launches above SMALL_LAUNCH_BLOCKS (measured: -3 % at 128 / 256 prompts, round 4; -1.8 / -2.9 % at the round-6 kernels), nobody below (there pacing costs 0.4 %: profiles/r6/12_*)
 
 namespace {
 
@@ -2293,7 +2287,6 @@ bool sys_supported(int B, int T, int cfg, bool split) {
 
 // ---- XCD placement (sys_place_stages, systolic_plan.hip) rests on the dispatcher handing workgroup i of a launch to XCD i % 8: checked
 // once per device by a probe launch of the pipeline's shape, here, and by every pipeline workgroup when it starts.
-std::atomic<int> g_xcd_local{1};  // measurement switch: ladiff_debug_set_xcd_local
 
 __global__ __launch_bounds__(512, 1) void xcd_probe_kernel(unsigned* xcc) {
     extern __shared__ char lds[];
@@ -2327,23 +2320,15 @@ static bool xcd_round_robin() {
 
 // The stage table for this call's pointers: the planner's, placed on the XCDs where the switch allows it and the probe found round robin.
 int sys_build_stages(const DenoiserW& W, const DenoiserW& WS, float* ws, int MR, int NB, std::vector<unsigned char>& host) {
-    return sys_build_stages(W, WS, ws, MR, NB, g_xcd_local && xcd_round_robin(), host);
+    return sys_build_stages(W, WS, ws, MR, NB, g_loop.xcd_local.load() && xcd_round_robin(), host);
 }
-
-// One launch = local steps [step_lo, step_lo + n) of the loop on the latents in `lat`.  The stage table must already be in
-// the workspace (sys_upload_stages); `ctab` holds the hoisted cross-attention rows of n_ctab >= n steps starting at step_lo.
-// waves per SIMD of the 16-row plan's stage workgroups (measurement switch: ladiff_debug_set_stage_waves)
-std::atomic<int> g_waves16{2};
-// hand-off protocol of the 16-row plan's eight-wave stages: 1 = parity tags in the data (default), 0 = flags (ladiff_debug_set_handoff)
-std::atomic<int> g_handoff{1};
-constexpr int LOOK_AHEAD_BLOCKS = 72;      // see `settle`: 58 blocks (128 prompts of mixed lengths) lose with it, 86 win
 
 namespace {
 // Every instantiation of the kernel, once: the launch opts each into its dynamic LDS and selects by the same rows.
-struct LoopKernel { int fp32, MR, waves, tagged; bool look_ahead; void (*fn)(const SysArgs); int threads; bool multistep, edit; };
-#define LOOP_KERNEL(AR, MR, WS, HO, EQ) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ>, 256 * WS, false, false}
-#define LOOP_KERNEL_MS(AR, MR, WS, HO, EQ) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ, true>, 256 * WS, true, false}
-#define LOOP_KERNEL_ED(AR, MR, WS, HO, EQ, MS) {AR, MR, WS, HO, EQ, systolic_loop_kernel<MR, AR, WS, HO, EQ, MS, true>, 256 * WS, MS, true}
+struct LoopKernel { LoopKey key; void (*fn)(const SysArgs); };      // launched with 256 x key.waves threads
+#define LOOP_KERNEL(AR, MR, WS, HO, EQ) {{MR, WS, HO == 1, EQ, AR == 1, false, false}, systolic_loop_kernel<MR, AR, WS, HO, EQ>}
+#define LOOP_KERNEL_MS(AR, MR, WS, HO, EQ) {{MR, WS, HO == 1, EQ, AR == 1, true, false}, systolic_loop_kernel<MR, AR, WS, HO, EQ, true>}
+#define LOOP_KERNEL_ED(AR, MR, WS, HO, EQ, MS) {{MR, WS, HO == 1, EQ, AR == 1, MS, true}, systolic_loop_kernel<MR, AR, WS, HO, EQ, MS, true>}
 const LoopKernel LOOP_KERNELS[] = {
     // flags: 16-row blocks with two waves per SIMD (ladiff_debug_set_handoff(0)) and 32-row blocks, split | fp32
     LOOP_KERNEL(0, 1, 2, 0, false), LOOP_KERNEL(0, 2, 1, 0, false), LOOP_KERNEL(1, 1, 2, 0, false), LOOP_KERNEL(1, 2, 1, 0, false),
@@ -2371,39 +2356,31 @@ int sys_reset_status(float* ws, hipStream_t s) {
     return 0;
 }
 
-int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab,
-                         const float* coef, const float* noise, float* lat, const int32_t* counts, float gscale, int B, int T,
-                         int step_lo, int n, int fp32, int MR, int NB, hipStream_t s, int cfg, int fault_wg, unsigned long long timeout_ticks,
-                         const NoiseGen& gen, const float* gscales, float* x0_prev, bool edit, const int32_t* starts, int first_step) {
-    // fault_wg / timeout_ticks: the caller's SAMPLER's fault injection (ladiff_sampler_set_fault; -1 / 0 = none / default bound)
+// One launch = local steps [step_lo, step_lo + n) of the loop on the latents in `lat`.  The stage table must already be in
+// the workspace (sys_upload_stages); `ctab` holds the hoisted cross-attention rows of n_ctab >= n steps starting at step_lo.
+// Which instantiation it takes and how its stages poll is sys_launch_policy's (systolic_plan.hip), from ONE snapshot of the switches.
+int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab, float* lat,
+                         const int32_t* counts, const StepEnd& e, int B, int T, int step_lo, int n, int fp32, int MR, int NB, hipStream_t s,
+                         int fault_wg, unsigned long long timeout_ticks) {
+    const LoopLaunch p = sys_launch_policy(MR, NB, fp32 != 0, e.x0_prev != nullptr, e.edit, g_loop.snapshot());
+    const LoopKernel* k = nullptr;
+    for (const LoopKernel& c : LOOP_KERNELS) if (c.key == p.key) k = &c;
+    if (k == nullptr) return LADIFF_ERR_UNSUPPORTED;       // before anything is enqueued
     const SysLayout L = sys_layout(MR, NB);
     SysArgs a;
     a.stages = reinterpret_cast<const Stage*>(ws + L.off_stages);
     a.blocks = reinterpret_cast<const BlockDesc*>(ws + L.off_blocks);
     a.flags = reinterpret_cast<unsigned*>(ws + L.off_flags);
     a.status = reinterpret_cast<unsigned*>(ws + L.off_status);
-    a.tables = tables; a.tkv = tkv; a.ctab = ctab; a.coef = coef; a.noise = noise; a.pe = W.query_pe; a.ng = W.norm.g; a.nb = W.norm.b;
-    a.lat = lat; a.x0p = x0_prev; a.starts = starts; a.first_step = first_step; a.counts = counts; a.gscale = gscale; a.gscales = gscales; a.B = B; a.B2 = cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
-    a.n_ctab = n_ctab;
-    a.split = cfg ? L.split : 0;       // no guidance: every block is a unit of its own (sys_pack_blocks)
-    a.force_mismatch = g_xcd_local == 2 ? 1 : 0;
-    a.fault_wg = fault_wg;
-    a.timeout_ticks = timeout_ticks > 0 ? timeout_ticks : TIMEOUT_TICKS;
-    const int la_from = g_look_ahead_from.load() >= 0 ? g_look_ahead_from.load() : LOOK_AHEAD_BLOCKS;      // ladiff_debug_set_loop_thresholds
-    const int small_upto = g_small_upto.load() >= 0 ? g_small_upto.load() : SMALL_LAUNCH_BLOCKS;
-    a.look_ahead = NB >= la_from ? 1 : 0;
-    a.gen = gen;
-    a.pause_mask = g_poll_pause.load() & 0xff; a.pause_len = (g_poll_pause.load() >> 8) & 0xff;
-    a.pace = g_pace.load() >= 0 ? g_pace.load() : (NB <= small_upto ? 0 : (4 | (4 << 8)));
-    // Small launches (a block's trip through the stages bounds the step, the stages wait for rows most of the time): the LIN and FFN
-    // workgroups idle ~0.25 us after every block before they start to poll for the next one's rows - those are being produced just then by
-    // a stage on the critical path (OUT / RED2), and eight workgroups loading its lines do not make it faster.  Measured (profiles/r4/14_*):
-    // loop -2.2 % at 32 ... 64 prompts and at 100 / 128 prompts of mixed lengths (<= 58 blocks), nothing from 65 blocks, a loss beyond.
-    const int sd = g_stage_delay.load();
-    if (sd < 0) { a.delay_mask = NB <= small_upto ? 1 | 8 : 0; a.delay_len = 4; }
-    else { a.delay_mask = sd & 0xff; a.delay_len = (sd >> 8) & 0x7f; }
-    a.probe = 0;
-    a.stamps = nullptr;
+    a.tables = tables; a.tkv = tkv; a.ctab = ctab; a.coef = e.coef; a.noise = e.noise; a.pe = W.query_pe; a.ng = W.norm.g; a.nb = W.norm.b;
+    a.lat = lat; a.x0p = e.x0_prev; a.starts = e.starts; a.first_step = e.first_step; a.counts = counts; a.gscale = e.g; a.gscales = e.gs; a.B = B; a.B2 = e.cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
+    a.n_ctab = n_ctab; a.gen = e.gen;
+    a.split = e.cfg ? L.split : 0;     // no guidance: every block is a unit of its own (sys_pack_blocks)
+    // fault_wg / timeout_ticks: the caller's SAMPLER's fault injection (ladiff_sampler_set_fault; -1 / 0 = none / default bound)
+    a.fault_wg = fault_wg; a.timeout_ticks = timeout_ticks > 0 ? timeout_ticks : TIMEOUT_TICKS;
+    a.force_mismatch = p.force_mismatch; a.look_ahead = p.look_ahead;
+    a.pause_mask = p.pause_mask; a.pause_len = p.pause_len; a.pace = p.pace; a.delay_mask = p.delay_mask; a.delay_len = p.delay_len;
+    a.probe = 0; a.stamps = nullptr;
 #ifdef LADIFF_STAMPS
     a.stamps = g_sys_stamps;
     a.probe = g_sys_probe;
@@ -2419,8 +2396,8 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     if (dev < 0 || dev >= 64) return LADIFF_ERR_ARG;
     std::lock_guard<std::mutex> lock(mu);
     if (!attr_set[dev]) {
-        for (const LoopKernel& k : LOOP_KERNELS)
-            LADIFF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, SYS_LDS_BYTES));
+        for (const LoopKernel& c : LOOP_KERNELS)
+            LADIFF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(c.fn), hipFuncAttributeMaxDynamicSharedMemorySize, SYS_LDS_BYTES));
         attr_set[dev] = true;
     }
     if (done[dev] == nullptr) LADIFF_HIP(hipEventCreateWithFlags(&done[dev], hipEventDisableTiming));
@@ -2429,23 +2406,13 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     // ladiff_diffusion_reverse call (sys_reset_status): a schedule longer than one window is several launches, and an abort in an
     // early window must neither be erased by the next launch's memset nor let the later windows iterate on corrupt latents.
     LADIFF_HIP(hipMemsetAsync(a.status + 8, 0, 2 * sizeof(unsigned), s));
-    const bool tagged = MR == 1 && g_waves16 == 2 && g_handoff == 1;
-    if (tagged) {
+    if (p.key.tagged) {
         // tagged hand-off: every word of the hand-off buffers starts with parity 1 (the first use of every slot expects 0)
         LADIFF_HIP(hipMemsetAsync(ws + L.off_xin0, 0x01, (L.total - L.off_xin0) * sizeof(float), s));
     } else {
         LADIFF_HIP(hipMemsetAsync(a.flags, 0, (L.off_xin0 - L.off_flags) * sizeof(float), s));
     }
-    // the key of LOOP_KERNELS: 32-row blocks have one form; look-ahead is a property of the tagged hand-off
-    const int mr = MR == 1 ? 1 : 2, waves = mr == 1 && g_waves16 == 2 ? 2 : 1;
-    const bool la = tagged && a.look_ahead;
-    const LoopKernel* k = nullptr;
-    for (const LoopKernel& c : LOOP_KERNELS)
-        if (c.fp32 == (fp32 ? 1 : 0) && c.MR == mr && c.waves == waves && c.tagged == (tagged ? 1 : 0) && c.look_ahead == la &&
-            c.multistep == (x0_prev != nullptr) && c.edit == edit)
-            k = &c;
-    if (k == nullptr) return LADIFF_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k->fn, dim3(L.nwg), dim3(k->threads), SYS_LDS_BYTES, s, a);
+    hipLaunchKernelGGL(k->fn, dim3(L.nwg), dim3(256 * k->key.waves), SYS_LDS_BYTES, s, a);
     LADIFF_LAUNCH_CHECK();
     LADIFF_HIP(hipEventRecord(done[dev], s));
     return 0;

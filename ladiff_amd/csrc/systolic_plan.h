@@ -31,7 +31,8 @@ constexpr int PRING = 16;
 constexpr int MAX_BP_BLOCKS = 2;            // consecutive blocks that make "all consumers" (Stage::bp_blocks <= this: red_plan's styl_groups)
 static_assert(PRING >= 2 && PRING % 2 == 0, "the back-pressure look-back is PRING / 2 blocks");
 static_assert(MAX_BP_BLOCKS <= PRING / 2, "every block a producer looks back at must be in the half ring it is about to leave alone");
-constexpr int SMALL_LAUNCH_BLOCKS = 60;     // launches up to this many blocks: LIN / FFN rest after every block (launch_systolic_loop)
+constexpr int SMALL_LAUNCH_BLOCKS = 60;     // launches up to this many blocks: LIN / FFN rest after every block (sys_launch_policy)
+constexpr int LOOK_AHEAD_BLOCKS = 72;       // launches from this many blocks look ahead (systolic.hip, `settle`): 58 blocks (128 prompts of mixed lengths) lose with it, 86 win
 constexpr int FLAG_STRIDE = 32;             // words between the flags of two producers: every flag on a 128-byte line of its own
 constexpr int SYS_LDS_BYTES = 100 * 1024;   // > 80 KiB: one workgroup per CU, so the <= 256 workgroups sit on distinct CUs
 constexpr int GROUPS_PER_LAYER = 7;
@@ -93,11 +94,33 @@ struct RedPlan { int red2_parts, styl_parts, styl_groups, out_groups; };
 constexpr RedPlan PLAN32{NRED, NRED, 1, 1}, PLAN16{2, 2, 2, 1}, PLAN16_OUT2{2, 2, 1, 2};
 static_assert(PLAN32.styl_groups <= MAX_BP_BLOCKS && PLAN16.styl_groups <= MAX_BP_BLOCKS && PLAN16_OUT2.styl_groups <= MAX_BP_BLOCKS,
               "a ring's producer looks back at styl_groups consecutive blocks (Stage::bp_blocks): see PRING");
-extern std::atomic<int> g_stage_plan;     // the measurement switch between the two (systolic.hip, ladiff_debug_set_stage_plan)
-inline RedPlan red_plan(int MR) {
-    if (MR != 1) return PLAN32;
-    return g_stage_plan.load() == 1 ? PLAN16_OUT2 : PLAN16;
+// The loop's measurement switches (include/ladiff_hip_debug.h, ladiff_debug_set_*): one process-wide object of atomics, defined in
+// systolic_plan.hip.  Every value they accept selects a launch form that the tests hold to the same tolerances; the timing builds that
+// produce garbage exist in the diagnostic twin only (-DLADIFF_STAMPS).  A launch reads them ONCE, as a LoopSwitches snapshot.
+struct LoopSwitches {
+    int waves16;                  // waves per SIMD of the 16-row plan's stage workgroups (ladiff_debug_set_stage_waves)
+    int handoff;                  // hand-off of the 16-row plan's eight-wave stages: 1 = parity tags in the data, 0 = flags (ladiff_debug_set_handoff)
+    int stage_plan;               // how a layer's spare workgroups are dealt (red_plan, ladiff_debug_set_stage_plan)
+    int poll_pause, stage_delay;  // ladiff_debug_set_poll_pause / _stage_delay (mask | len << 8); stage_delay -1: by block count
+    // ladiff_debug_set_pacing (eighths | mask << 8); -1: by block count - STYL sleeps half of its last observed wait before polling in launches above SMALL_LAUNCH_BLOCKS
+    // (measured: -3 % at 128 / 256 prompts, round 4; -1.8 / -2.9 % at the round-6 kernels), nobody below (there pacing costs 0.4 %: profiles/r6/12_*)
+    int pace;
+    int look_ahead_from, small_upto;      // ladiff_debug_set_loop_thresholds (-1: LOOK_AHEAD_BLOCKS / SMALL_LAUNCH_BLOCKS)
+    int xcd_local;                // ladiff_debug_set_xcd_local: 0 = no XCD placement, 1 = placed, 2 = placed and every workgroup reports a mismatch
+};
+struct LoopSwitchAtoms {
+    std::atomic<int> waves16{2}, handoff{1}, stage_plan{0}, poll_pause{0}, stage_delay{-1}, pace{-1}, look_ahead_from{-1}, small_upto{-1}, xcd_local{1};
+    LoopSwitches snapshot() const { return {waves16, handoff, stage_plan, poll_pause, stage_delay, pace, look_ahead_from, small_upto, xcd_local}; }
+};
+extern LoopSwitchAtoms g_loop;
+inline RedPlan red_plan(int MR) { return MR != 1 ? PLAN32 : g_loop.stage_plan == 1 ? PLAN16_OUT2 : PLAN16; }
+// sys_launch_policy's result: the key of the kernel instantiation (the rows of LOOP_KERNELS, systolic.hip) and the policy words of SysArgs
+struct LoopKey { int mr, waves; bool tagged, look_ahead, fp32, multistep, edit; };   // mr: 1 | 2 = 16- | 32-row blocks (one form); waves per SIMD; look-ahead only with the tagged hand-off
+inline bool operator==(const LoopKey& a, const LoopKey& b) {
+    return a.mr == b.mr && a.waves == b.waves && a.tagged == b.tagged && a.look_ahead == b.look_ahead && a.fp32 == b.fp32 && a.multistep == b.multistep && a.edit == b.edit;
 }
+struct LoopLaunch { LoopKey key; int look_ahead, pace, delay_mask, delay_len, pause_mask, pause_len, force_mismatch; };
+LoopLaunch sys_launch_policy(int MR, int NB, bool fp32, bool multistep, bool edit, const LoopSwitches& sw);
 
 struct SysLayout {
     size_t blk, ring;             // floats of one [NB][RT][256] buffer / of one [PRING][RT][256] partial plane

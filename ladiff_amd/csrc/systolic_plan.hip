@@ -8,6 +8,8 @@
 
 namespace ladiff {
 
+LoopSwitchAtoms g_loop;
+
 int plan_nwg(int MR) {
     const RedPlan rp = red_plan(MR);
     return NL * (4 + rp.out_groups + NSLICE + rp.red2_parts + NSLICE + rp.styl_parts * rp.styl_groups) + 2 * NSKIP + NTAIL;
@@ -301,6 +303,24 @@ void choose_plan(int B, int T, const int32_t* h_counts, bool masked, int loop_mo
     }
     if (want == 1 && mr16 == 1) { plan.swap(p16); *plan_mr = 1; *plan_nb = nb16; }
     else { plan.swap(p32); *plan_mr = 2; *plan_nb = nb32; }
+}
+
+LoopLaunch sys_launch_policy(int MR, int NB, bool fp32, bool multistep, bool edit, const LoopSwitches& sw) {
+    const int la_from = sw.look_ahead_from >= 0 ? sw.look_ahead_from : LOOK_AHEAD_BLOCKS;      // ladiff_debug_set_loop_thresholds
+    const int small_upto = sw.small_upto >= 0 ? sw.small_upto : SMALL_LAUNCH_BLOCKS;
+    LoopLaunch p;
+    p.look_ahead = NB >= la_from ? 1 : 0;               // whether tagged or not
+    const bool tagged = MR == 1 && sw.waves16 == 2 && sw.handoff == 1;
+    p.key = LoopKey{MR == 1 ? 1 : 2, MR == 1 && sw.waves16 == 2 ? 2 : 1, tagged, tagged && p.look_ahead, fp32, multistep, edit};
+    p.pause_mask = sw.poll_pause & 0xff; p.pause_len = (sw.poll_pause >> 8) & 0xff; p.force_mismatch = sw.xcd_local == 2 ? 1 : 0;
+    p.pace = sw.pace >= 0 ? sw.pace : (NB <= small_upto ? 0 : (4 | (4 << 8)));
+    // Small launches (a block's trip through the stages bounds the step, the stages wait for rows most of the time): the LIN and FFN
+    // workgroups idle ~0.25 us after every block before they start to poll for the next one's rows - those are being produced just then by
+    // a stage on the critical path (OUT / RED2), and eight workgroups loading its lines do not make it faster.  Measured (profiles/r4/14_*):
+    // loop -2.2 % at 32 ... 64 prompts and at 100 / 128 prompts of mixed lengths (<= 58 blocks), nothing from 65 blocks, a loss beyond.
+    if (sw.stage_delay < 0) { p.delay_mask = NB <= small_upto ? 1 | 8 : 0; p.delay_len = 4; }
+    else { p.delay_mask = sw.stage_delay & 0xff; p.delay_len = (sw.stage_delay >> 8) & 0x7f; }
+    return p;
 }
 
 }  // namespace ladiff

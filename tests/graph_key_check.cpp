@@ -106,16 +106,26 @@ int main() {
             CHECK(sampler_key(b, 3, pipeline, 1, 6, off) != sampler_key(a, 3, pipeline, 1, 6, off));
         }
 
-    // the decode graph's key: the five measurement switches are entries of their own
+    // the decode graph's key: every field of the switch snapshot is an entry of its own
     auto dkey = [&](int sw, int v) {
-        int q[5] = {1, 1, 1, 0, 1};
+        int q[6] = {1, 1, 1, 1, 1, 0};      // fused_mlp, small_rows_path, final_split, out_cross, fused_attn, mlp_variant
         if (sw >= 0) q[sw] = v;
         return decode_key(W_TAB, S_TAB, 3, 1, P(30), (const int32_t*)P(31), (const int32_t*)P(32), nullptr, 0, 2, 60, 5, 263, P(33), slab + 34,
-                          slab + 35, q[0], q[1], q[2], q[3], q[4]);
+                          slab + 35, DecSwitches{q[0], q[1], q[2], q[3], q[4], q[5]});
     };
     CHECK(dkey(-1, 0) == dkey(-1, 0));
-    for (int sw = 0; sw < 5; ++sw) CHECK(dkey(sw, 2) != dkey(-1, 0));
+    for (int sw = 0; sw < 6; ++sw) CHECK(dkey(sw, 2) != dkey(-1, 0));
     CHECK(dkey(0, 0) != dkey(1, 0));          // switches that the multiplied-up sum could have folded together stay apart
+    {
+        // two snapshots that differ only in out_cross (ladiff_debug_set_decoder_fusion + 64) give different keys
+        DecSwitches a0{1, 1, 1, 1, 1, 0}, a1 = a0;
+        a1.out_cross = 0;
+        auto key_of = [&](const DecSwitches& q) {
+            return decode_key(W_TAB, S_TAB, 3, 1, P(30), (const int32_t*)P(31), (const int32_t*)P(32), nullptr, 0, 2, 60, 5, 263, P(33), slab + 34,
+                              slab + 35, q);
+        };
+        CHECK(key_of(a0) != key_of(a1) && key_of(a0) == key_of(a0) && key_of(a1) == key_of(a1));
+    }
     CHECK(dkey(-1, 0) != sampler_key(a, 3, true, 1, 6, off));
     std::printf("graph_key_check: ok\n");
     return 0;

@@ -1,19 +1,19 @@
 // Host-only check of the loop kernel's planner (ladiff_amd/csrc/systolic_plan.hip): builds workspace layouts, block lists and stage
-// tables on a fake workspace base and holds them to the properties the device code relies on.  No HIP call, no GPU; test_planner.py
-// compiles this file together with the planner under AddressSanitizer + UBSan and runs it as a child process (exit status 0 = all held).
+// tables on a fake workspace base and holds them to the properties the device code relies on, and holds the launch policy
+// (sys_launch_policy) to its rule.  No HIP call, no GPU; test_planner.py compiles this file together with the planner under
+// AddressSanitizer + UBSan and runs it as a child process (exit status 0 = all held).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <set>
+#include <tuple>
 #include <utility>
 #include <vector>
 
 #include "systolic_plan.h"
 
-namespace ladiff {
-std::atomic<int> g_stage_plan{0};     // systolic.hip's switch (that file is device code and is not linked here)
-}
 using namespace ladiff;
 
 static int g_failed = 0;
@@ -42,7 +42,7 @@ static size_t round64(size_t f) { return (f + 63) / 64 * 64; }
 
 // ------------------------------------------------------------------ layout
 static void check_layout(int MR, int NB) {
-    std::snprintf(g_ctx, sizeof(g_ctx), "layout MR %d NB %d plan %d", MR, NB, g_stage_plan.load());
+    std::snprintf(g_ctx, sizeof(g_ctx), "layout MR %d NB %d plan %d", MR, NB, g_loop.stage_plan.load());
     const SysLayout L = sys_layout(MR, NB);
     const size_t off[] = {L.off_stages, L.off_status, L.off_blocks, L.off_flags, L.off_xin0, L.off_xs, L.off_xo,
                           L.off_att, L.off_x1, L.off_x2, L.off_pc, L.off_pe};                                    // carve order
@@ -65,7 +65,7 @@ static void check_layout(int MR, int NB) {
 
 // ------------------------------------------------------------------ stage table
 static void check_stages(int MR, int NB) {
-    std::snprintf(g_ctx, sizeof(g_ctx), "stages MR %d NB %d plan %d", MR, NB, g_stage_plan.load());
+    std::snprintf(g_ctx, sizeof(g_ctx), "stages MR %d NB %d plan %d", MR, NB, g_loop.stage_plan.load());
     static_assert(sizeof(Stage) == 20 * sizeof(int) + 11 * sizeof(void*), "no padding: the tables are compared as bytes");
     const DenoiserW W = fake_weights(uintptr_t(2) << 44), WSP = fake_weights(uintptr_t(3) << 44);
     const SysLayout L = sys_layout(MR, NB);
@@ -138,7 +138,7 @@ static int clamp_count(int c, int T) { return c > T ? T : (c < 1 ? 1 : c); }
 
 // one sys_pack_blocks call: returns (mr, nb) through the arguments after checking the block list
 static void check_pack(const Case& c, int want_mr, bool cfg, int* mr_out, int* nb_out) {
-    std::snprintf(g_ctx, sizeof(g_ctx), "pack %s want_mr %d cfg %d plan %d", c.name, want_mr, (int)cfg, g_stage_plan.load());
+    std::snprintf(g_ctx, sizeof(g_ctx), "pack %s want_mr %d cfg %d plan %d", c.name, want_mr, (int)cfg, g_loop.stage_plan.load());
     const int B = c.B, T = c.T;
     const int32_t* h_counts = (c.masked && !c.device_only) ? c.counts.data() : nullptr;
     std::vector<unsigned char> raw;
@@ -241,7 +241,76 @@ static void check_case(const Case& c, std::set<std::pair<int, int>>& plans) {
             }
 }
 
+// ------------------------------------------------------------------ launch policy
+// sys_launch_policy against its rule, restated here (constants as numbers): every field, over the shapes on both sides of the two
+// block-count thresholds and every switch value that takes another branch.
+static void check_policy() {
+    {
+        std::snprintf(g_ctx, sizeof(g_ctx), "switch snapshot");
+        const LoopSwitches d = g_loop.snapshot();                          // the library's defaults
+        CHECK(d.waves16 == 2 && d.handoff == 1 && d.stage_plan == 0 && d.poll_pause == 0 && d.stage_delay == -1 && d.pace == -1 &&
+              d.look_ahead_from == -1 && d.small_upto == -1 && d.xcd_local == 1);
+        g_loop.pace = 3 | 5 << 8; g_loop.xcd_local = 2;
+        const LoopSwitches e = g_loop.snapshot();
+        CHECK(e.pace == (3 | 5 << 8) && e.xcd_local == 2 && e.waves16 == 2 && e.stage_delay == -1);
+        g_loop.pace = -1; g_loop.xcd_local = 1;
+    }
+    // (MR, fp32, multistep, edit, waves16, handoff, look_ahead) -> the key first seen for it
+    std::map<std::tuple<int, bool, bool, bool, int, int, int>, LoopKey> keys;
+    long n = 0;
+    for (int MR : {1, 2}) for (bool fp32 : {false, true}) for (bool ms : {false, true}) for (bool edit : {false, true})
+    for (int NB : {1, 59, 60, 61, 71, 72, 73, 255})
+    for (int waves16 : {1, 2}) for (int handoff : {0, 1})
+    for (int la_sw : {-1, 0, 66}) for (int small_sw : {-1, 0, 66})
+    for (int pace : {-1, 0, 3 | 5 << 8}) for (int sd : {-1, 0, 9 | 4 << 8}) for (int pp : {0, 0xff | 64 << 8})
+    for (int xcd_local : {0, 1, 2}) {
+        std::snprintf(g_ctx, sizeof(g_ctx), "policy MR %d fp32 %d ms %d edit %d NB %d waves %d handoff %d la %d small %d pace %d sd %d pp %d xcd %d",
+                      MR, (int)fp32, (int)ms, (int)edit, NB, waves16, handoff, la_sw, small_sw, pace, sd, pp, xcd_local);
+        const LoopSwitches sw{waves16, handoff, 0, pp, sd, pace, la_sw, small_sw, xcd_local};
+        const LoopLaunch p = sys_launch_policy(MR, NB, fp32, ms, edit, sw);
+        ++n;
+        const bool tagged = MR == 1 && waves16 == 2 && handoff == 1;
+        const int la_from = la_sw >= 0 ? la_sw : 72, small = small_sw >= 0 ? small_sw : 60;
+        const int look_ahead = NB >= la_from ? 1 : 0;
+        CHECK(p.key.tagged == tagged);
+        CHECK(p.key.waves == ((MR == 1 && waves16 == 2) ? 2 : 1));
+        CHECK(p.key.mr == (MR == 1 ? 1 : 2));
+        CHECK(p.look_ahead == look_ahead);
+        CHECK(p.key.look_ahead == (tagged && look_ahead != 0));
+        CHECK(p.key.fp32 == fp32 && p.key.multistep == ms && p.key.edit == edit);
+        CHECK(p.pace == (pace >= 0 ? pace : (NB <= small ? 0 : (4 | 4 << 8))));
+        if (sd < 0) CHECK(p.delay_mask == (NB <= small ? (1 | 8) : 0) && p.delay_len == 4);
+        else CHECK(p.delay_mask == (sd & 0xff) && p.delay_len == ((sd >> 8) & 0x7f));
+        CHECK(p.pause_mask == (pp & 0xff) && p.pause_len == ((pp >> 8) & 0xff));
+        CHECK(p.force_mismatch == (xcd_local == 2 ? 1 : 0));
+        // the key is a function of these seven and of nothing else
+        const auto in = std::make_tuple(MR, fp32, ms, edit, waves16, handoff, look_ahead);
+        const auto it = keys.find(in);
+        if (it == keys.end()) keys.emplace(in, p.key);
+        else {
+            const LoopKey& k = it->second;                                 // field by field here, and by the library's operator==
+            CHECK(k.mr == p.key.mr && k.waves == p.key.waves && k.tagged == p.key.tagged && k.look_ahead == p.key.look_ahead &&
+                  k.fp32 == p.key.fp32 && k.multistep == p.key.multistep && k.edit == p.key.edit);
+            CHECK(k == p.key);
+        }
+    }
+    {
+        std::snprintf(g_ctx, sizeof(g_ctx), "key equality");              // every field takes part
+        const LoopKey k{1, 2, true, true, false, true, false};
+        for (int f = 0; f < 7; ++f) {
+            LoopKey o = k;
+            if (f == 0) o.mr = 2; else if (f == 1) o.waves = 1; else if (f == 2) o.tagged = false; else if (f == 3) o.look_ahead = false;
+            else if (f == 4) o.fp32 = true; else if (f == 5) o.multistep = false; else o.edit = true;
+            CHECK(!(o == k) && o == o);
+        }
+    }
+    std::snprintf(g_ctx, sizeof(g_ctx), "policy enumeration");
+    CHECK(n == 2L * 2 * 2 * 2 * 8 * 2 * 2 * 3 * 3 * 3 * 3 * 2 * 3 && keys.size() == 2u * 2 * 2 * 2 * 2 * 2 * 2);
+    CHECK(LOOK_AHEAD_BLOCKS == 72 && SMALL_LAUNCH_BLOCKS == 60);
+}
+
 int main() {
+    check_policy();
     std::vector<Case> cases;
     cases.push_back({"1: B 1 T 1", 1, 1, {}, false, false});
     cases.push_back({"2: B 1 T 7", 1, 7, {}, false, false});
@@ -261,7 +330,7 @@ int main() {
     cases.push_back({"9b: B 6 T 3 counts", 6, 3, {3, 1, 2, 3, 1, 1}, true, false});
 
     for (int plan = 0; plan <= 1; ++plan) {                                // both ways of dealing a layer's spare workgroups (red_plan)
-        g_stage_plan = plan;
+        g_loop.stage_plan = plan;
         std::set<std::pair<int, int>> plans;                               // every (MR, NB) the packing came up with
         for (const Case& c : cases) check_case(c, plans);
         for (int MR = 1; MR <= 2; ++MR)

@@ -113,5 +113,18 @@ def test_decode_graph_captures_when_the_key_or_the_epoch_changes_and_only_then(n
             L.ladiff_debug_set_decoder_fusion(1)
         again, n = counted(lambda: vae.decode(z, lens))
         assert n == 1 and torch.equal(again, first)             # the switch is back: the key changed again
+        try:
+            assert L.ladiff_debug_set_decoder_fusion(1 + 64) == 0  # out_proj + cross-attention as two launches: part of the key as well
+            crossed, n = counted(lambda: vae.decode(z, lens))
+            print(f"decode: after the out_cross switch flipped: +{n}")
+            assert n == 1
+            vae.graph_rows = 0                                  # the same decode launched directly, under the same switch
+            direct, n = counted(lambda: vae.decode(z, lens))
+            assert n == 0 and torch.equal(crossed, direct)
+        finally:
+            vae.graph_rows = 4096
+            L.ladiff_debug_set_decoder_fusion(1)
+        again, n = counted(lambda: vae.decode(z, lens))
+        assert n == 1 and torch.equal(again, first)             # switched back: captured once more, the first result again
     finally:
         vae.graph_rows, vae.precision = old_rows, old_precision

@@ -1,4 +1,4 @@
-"""The loop kernel's host planner (csrc/systolic_plan.hip: workspace carve, block packing, stage table, XCD placement) on the CPU:
+"""The loop kernel's host planner (csrc/systolic_plan.hip: workspace carve, block packing, stage table, XCD placement, launch policy) on the CPU:
 tests/planner_check.cpp and the planner unit, compiled as plain C++17 with AddressSanitizer + UBSan into a stand-alone program that
 runs as a child process.  No GPU, no HIP, nothing loaded into this interpreter."""
 import os

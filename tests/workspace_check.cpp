@@ -8,9 +8,6 @@
 
 #include "workspace.h"
 
-namespace ladiff {
-std::atomic<int> g_stage_plan{0};     // systolic.hip's switch (that file is device code and is not linked here)
-}
 using namespace ladiff;
 
 static int g_failed = 0;
