@@ -25,6 +25,8 @@ logit std min ... max over the layers | model's largest |logit| | mean largest p
       denoiser linear cross-attn, 64 columns   std  0.97 ...  1.02 | max   4.5 | largest probability 0.10 ... 0.11
       encoder self-attention, 206 keys         std  0.48 ...  0.70 | max   3.7 | largest probability 0.02 ... 0.04
       CLIP self-attention, 2 layers            std  0.83 ...  0.95 | max   5.4 | largest probability 0.12 ... 0.17
+      denoiser token-axis softmax, N = 2 / 77  std  0.98 ...  1.04 | max   4.9 | largest probability 0.69 ... 0.70 / 0.07 ... 0.07
+      denoiser self-attention, 8 / 83 keys     std  0.39 ...  0.88 | max   4.3 | largest probability 0.30 ... 0.35 / 0.03 ... 0.03
     trained_like(sd, 1):
       decoder self-attention, 196 keys         std  3.09 ... 23.21 | max  68.7 | largest probability 0.28 ... 0.69
       decoder cross-attention, 5 keys          std  9.42 ... 12.49 | max  43.8 | largest probability 0.96 ... 0.97
@@ -32,6 +34,12 @@ logit std min ... max over the layers | model's largest |logit| | mean largest p
       denoiser linear cross-attn, 64 columns   std  3.33 ...  4.05 | max  16.0 | largest probability 0.44 ... 0.59
       encoder self-attention, 206 keys         std 10.82 ... 18.50 | max  89.3 | largest probability 0.66 ... 0.83
       CLIP self-attention, 2 layers            std 11.24 ... 12.63 | max  59.0 | largest probability 0.80 ... 0.85
+      denoiser token-axis softmax, N = 2 / 77  std  3.40 ...  3.99 | max  18.5 | largest probability 0.86 ... 0.88 / 0.39 ... 0.44
+      denoiser self-attention, 8 / 83 keys     std  3.98 ... 13.44 | max  85.5 | largest probability 0.78 ... 0.87 / 0.46 ... 0.62
+
+(The last two lines of each block: a text SEQUENCE per prompt, tests/ntext_cases.py `tokens2` / `tokens77` - 4 samples x 5 latents, N text
+tokens: the softmax over the N tokens per feature of the linear cross-attention's keys, and the self-attention over T + N + 1 keys;
+tests/test_ntext_cases.py prints them per case.)
 
 The oracle's own fp32-vs-fp64 error e32 on these cases: decode 4.6e-5 (synthetic 3.7e-6), denoiser 1.8e-5 (synthetic 3.4e-6); outputs finite,
 max |frame| 5.3, max |eps| 6.7, largest weight 6.6.  One gain for all models could not meet the conditions together: the decoder needs
