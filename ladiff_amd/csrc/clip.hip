@@ -11,7 +11,6 @@
 // batch for prompts of 1 .. 30 words; q / k / v are one batched GEMM launch.  Large GEMMs go through launch_gemm (fp32 MFMA, or f16x3 with S-format
 // operands when a split weight table is given); the attention core is the decoder's MFMA kernel with 12 heads + causal.
 #include "model.h"
-#include "gemm_kr.h"
 
 namespace ladiff {
 
@@ -159,95 +158,75 @@ int clip_text_encode(const ClipW& w, const ClipW* wsp, int n_layers, int vocab, 
     if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     if (B == 0) return 0;
     const bool sp = wsp != nullptr;
-    float *x = a.x, *x2 = a.x2, *h = a.h, *qkv = a.qkv, *att = a.att, *mlp = a.mlp, *planes = a.planes, *pooled = a.pooled;
-    int32_t* eos = a.eos;
+    const Seq c{sp, M, s};
+    const ClipW& wm = mfma_table(w, wsp);
+    float *x = a.x, *x2 = a.x2, *qkv = a.qkv, *planes = a.planes, *pooled = a.pooled;
+    const Twin h = operand_only(sp, a.h), att = operand_only(sp, a.att), mlp = operand_only(sp, a.mlp);      // read by matrix products only
     const bool small = sp && M <= CLIP_SMALL_ROWS;
 
     // small-row path: S-format A [M, K] x S-format W [N, K] -> K / 256 planes (row stride ld, written at column col0) ...
-    auto kr_planes = [&](const float* A, int K, const float* Wsp, int N, int ld, int col0) -> int {
-        KrArgs g;
-        g.A = A; g.lda = K; g.W = Wsp; g.ldw = K; g.Y = planes + col0; g.ldy = ld; g.M = M; g.N = N; g.K = K; g.split = 1;
+    auto kr_planes = [&](Twin A, int K, const LinearW& W, int N, int ld, int col0) -> int {
         if (K == 256) return LADIFF_ERR_SHAPE;   // (a single slice would apply the epilogue itself: not a shape of this tower)
-        return launch_gemm_kr(g, s);
+        return launch_gemm_kr(proj_kr(c, A, K, LinearW{W.w, nullptr}, Twin{planes + col0, nullptr}, ld, N), s);
     };
-    // ... and their sum + bias, activation, residual
-    auto reduce = [&](int K, int N, int ld, const float* bias, int act, const float* res, int ldres, float* Y, float* Ys, int ldy) -> int {
+    // ... and the sum of `np` planes [M][ld] from `base` + bias, activation, residual
+    auto reduce = [&](const float* base, int np, int ld, int N, const float* bias, int act, const float* res, int ldres, Twin y, int ldy) -> int {
         const size_t n = (size_t)M * (N / 4);
-        hipLaunchKernelGGL(clip_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes, K / 256, (size_t)M * ld, ld, M, N, bias, act,
-                           res, ldres, Y, Ys, ldy);
+        hipLaunchKernelGGL(clip_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, base, np, (size_t)M * ld, ld, M, N, bias, act,
+                           res, ldres, y.f, y.s, ldy);
         LADIFF_LAUNCH_CHECK();
         return 0;
     };
-    auto gemm = [&](const float* A, int K, const LinearW& l, const LinearW& ls, float* Y, int ldy, int N, int act,
-                    const float* res, bool split_out) -> int {
+    auto gemm = [&](Twin A, int K, const LinearW& W, Twin y, int ldy, int N, int act, const float* res) -> int {
         if (small) {
-            LADIFF_TRY(kr_planes(A, K, ls.w, N, N, 0));
-            return reduce(K, N, N, l.b, act, res, ldy, split_out ? nullptr : Y, split_out ? Y : nullptr, ldy);
+            LADIFF_TRY(kr_planes(A, K, W, N, N, 0));
+            return reduce(planes, K / 256, N, N, W.b, act, res, ldy, y, ldy);
         }
-        GemmArgs g;
-        g.A = A; g.lda = K; g.W = sp ? ls.w : l.w; g.ldw = K; g.bias = l.b; g.M = M; g.N = N; g.K = K; g.act = act; g.ldy = ldy;
-        g.res = res; g.ldres = ldy; g.split = sp ? 1 : 0;
-        if (sp && split_out) g.Ys = Y; else g.Y = Y;
+        GemmArgs g = proj(c, A, K, W, y, ldy, N, act);
+        g.res = res; g.ldres = ldy;
         return launch_gemm(g, s);
     };
 
     hipLaunchKernelGGL(clip_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, s, ids, w.tok, w.pos, vocab, B, M, S, L, row_seq, row_off, x);
     LADIFF_LAUNCH_CHECK();
     if (!ragged) {
-        hipLaunchKernelGGL(clip_eos_kernel, dim3(B), dim3(64), 0, s, ids, S, L, eos);
+        hipLaunchKernelGGL(clip_eos_kernel, dim3(B), dim3(64), 0, s, ids, S, L, a.eos);
         LADIFF_LAUNCH_CHECK();
     }
 
     for (int l = 0; l < n_layers; ++l) {                       // CLIPEncoderLayer.forward (pre-LN residual blocks)
-        const ClipLayerW& W = w.layer[l];
-        const ClipLayerW& Ws = sp ? wsp->layer[l] : w.layer[l];
-        LADIFF_TRY(ln_rows(x, nullptr, 0, W.ln1, M, sp ? nullptr : h, sp ? h : nullptr, s));
+        const ClipLayerW W = mixed(w.layer[l], wm.layer[l]);
+        const LinearW* lw[3] = {&W.q, &W.k, &W.v};
+        LADIFF_TRY(ln_rows(x, nullptr, 0, W.ln1, M, h.f, h.s, s));
         // q | k | v packed by columns; the 1/sqrt(64) query scale is applied (exactly) inside the attention kernel.  One batched
         // launch of the three same-shape products (each alone leaves half of the chip idle at a few thousand rows)
-        if (small) {                             // q | k | v: three launches into one set of planes [3][M][2304], one row pass (the biases differ per part)
-            const LinearW* lw[3] = {&W.q, &W.k, &W.v};
-            const LinearW* lws[3] = {&Ws.q, &Ws.k, &Ws.v};
-            for (int i = 0; i < 3; ++i) LADIFF_TRY(kr_planes(h, CW, lws[i]->w, CW, 3 * CW, i * CW));
-            for (int i = 0; i < 3; ++i) {
-                const size_t n = (size_t)M * (CW / 4);
-                hipLaunchKernelGGL(clip_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes + i * CW, CW / 256, (size_t)M * 3 * CW,
-                                   3 * CW, M, CW, lw[i]->b, (int)ACT_NONE, (const float*)nullptr, 0, qkv + i * CW, (float*)nullptr, 3 * CW);
-                LADIFF_LAUNCH_CHECK();
-            }
+        if (small) {                             // q | k | v: three launches into one set of planes [3][M][2304], one row pass each (the biases differ per part)
+            for (int i = 0; i < 3; ++i) LADIFF_TRY(kr_planes(h, CW, *lw[i], CW, 3 * CW, i * CW));
+            for (int i = 0; i < 3; ++i)
+                LADIFF_TRY(reduce(planes + i * CW, CW / 256, 3 * CW, CW, lw[i]->b, ACT_NONE, nullptr, 0, Twin{qkv + i * CW, nullptr}, 3 * CW));
         } else {
             GemmArgs g3[3];
-            const LinearW* lw[3] = {&W.q, &W.k, &W.v};
-            const LinearW* lws[3] = {&Ws.q, &Ws.k, &Ws.v};
-            for (int i = 0; i < 3; ++i) {
-                GemmArgs& g = g3[i];
-                g.A = h; g.lda = CW; g.W = sp ? lws[i]->w : lw[i]->w; g.ldw = CW; g.bias = lw[i]->b; g.M = M; g.N = CW; g.K = CW; g.ldy = 3 * CW;
-                g.Y = qkv + i * CW; g.split = sp ? 1 : 0;
-            }
+            for (int i = 0; i < 3; ++i) g3[i] = proj(c, h, CW, *lw[i], Twin{qkv + i * CW, nullptr}, 3 * CW, CW);
             LADIFF_TRY(launch_gemm_batch(g3, 3, s));
         }
-        if (sp) LADIFF_TRY(launch_self_attention_split(qkv, seq_len, nullptr, att, B, L, CH, 1, 1, s, row_off, 0));
-        else LADIFF_TRY(launch_self_attention(qkv, seq_len, nullptr, att, B, L, CH, 1, 0, s, row_off));
-        LADIFF_TRY(gemm(att, CW, W.o, Ws.o, x2, CW, CW, ACT_NONE, x, false));             // x2 = x + out_proj(attn)
-        LADIFF_TRY(ln_rows(x2, nullptr, 0, W.ln2, M, sp ? nullptr : h, sp ? h : nullptr, s));
-        LADIFF_TRY(gemm(h, CW, W.fc1, Ws.fc1, mlp, CFF, CFF, ACT_QGELU, nullptr, true));  // quick_gelu(fc1)
-        if (sp && !small && M <= CLIP_FC2_KPARTS_MAX_ROWS) {                             // x = x2 + fc2(...), fc2 in K parts
-            GemmArgs g;
-            g.A = mlp; g.lda = CFF; g.W = Ws.fc2.w; g.ldw = CFF; g.M = M; g.N = CW; g.K = CFF; g.ldy = CW; g.split = 1;
-            g.Y = planes; g.ksplit = CLIP_FC2_KPARTS; g.plane = (size_t)M * CW;
+        if (sp) LADIFF_TRY(launch_self_attention_split(qkv, seq_len, nullptr, att.s, B, L, CH, 1, 1, s, row_off, 0));
+        else LADIFF_TRY(launch_self_attention(qkv, seq_len, nullptr, att.f, B, L, CH, 1, 0, s, row_off));
+        LADIFF_TRY(gemm(att, CW, W.o, Twin{x2, nullptr}, CW, CW, ACT_NONE, x));             // x2 = x + out_proj(attn)
+        LADIFF_TRY(ln_rows(x2, nullptr, 0, W.ln2, M, h.f, h.s, s));
+        LADIFF_TRY(gemm(h, CW, W.fc1, mlp, CFF, CFF, ACT_QGELU, nullptr));                 // quick_gelu(fc1)
+        if (sp && !small && M <= CLIP_FC2_KPARTS_MAX_ROWS) {                              // x = x2 + fc2(...), fc2 in K parts
+            GemmArgs g = proj(c, mlp, CFF, LinearW{W.fc2.w, nullptr}, Twin{planes, nullptr}, CW, CW);
+            g.ksplit = CLIP_FC2_KPARTS; g.plane = (size_t)M * CW;
             LADIFF_TRY(launch_gemm(g, s));
-            const size_t n = (size_t)M * (CW / 4);
-            hipLaunchKernelGGL(clip_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, planes, CLIP_FC2_KPARTS, (size_t)M * CW, CW, M, CW,
-                               W.fc2.b, (int)ACT_NONE, (const float*)x2, CW, x, (float*)nullptr, CW);
-            LADIFF_LAUNCH_CHECK();
-        } else
-        LADIFF_TRY(gemm(mlp, CFF, W.fc2, Ws.fc2, x, CW, CW, ACT_NONE, x2, false));        // x = x2 + fc2(...)
+            LADIFF_TRY(reduce(planes, CLIP_FC2_KPARTS, CW, CW, W.fc2.b, ACT_NONE, x2, CW, Twin{x, nullptr}, CW));
+        } else {
+            LADIFF_TRY(gemm(mlp, CFF, W.fc2, Twin{x, nullptr}, CW, CW, ACT_NONE, x2));      // x = x2 + fc2(...)
+        }
     }
     // pooled = final_layer_norm(x)[b, eos[b]];  text_embeds = text_projection(pooled)   (fp32: B rows only)
     if (ragged) LADIFF_TRY(ln_rows(x, row_off + 1, 0, w.final_ln, B, pooled, nullptr, s, -1));     // the prompt's last row = its EOS position
-    else LADIFF_TRY(ln_rows(x, eos, L, w.final_ln, B, pooled, nullptr, s));
-    GemmArgs g;
-    g.A = pooled; g.lda = CW; g.W = w.proj; g.ldw = CW; g.Y = out; g.ldy = CW; g.M = B; g.N = CW; g.K = CW;
-    return launch_gemm(g, s);
+    else LADIFF_TRY(ln_rows(x, a.eos, L, w.final_ln, B, pooled, nullptr, s));
+    return launch_gemm(lin(pooled, CW, w.proj, nullptr, out, CW, B, CW, CW), s);
 }
 
 }  // namespace ladiff

@@ -264,141 +264,112 @@ int denoiser_forward(const DenoiserW& w, const DenoiserW* wsp, const float* tabl
     if (ws_floats < a.total) return LADIFF_ERR_WORKSPACE;
     eps += (size_t)b_lo * T * D;
     const bool sp = wsp != nullptr;
-    const size_t MD = (size_t)M * D;
-    if (!sp) { for (float*& t : a.Ps) t = nullptr; for (float*& t : a.SKs) t = nullptr; }      // fp32 mode: no S-format twins
-    float *const *P = a.P, *const *SK = a.SK, *const *Ps = a.Ps, *const *SKs = a.SKs;
+    const Seq c{sp, M, s};
+    const DenoiserW& wm = mfma_table(w, wsp);      // matrices as the MFMA reads them
+    Twin P[4], SK[NSKIP];
+    pair_up(sp, a.P, a.Ps, P); pair_up(sp, a.SK, a.SKs, SK);
     float *qkv = a.qkv, *att = a.att, *hid = a.hid, *part = a.part;
+    const Twin hid_x = operand_only(sp, hid);       // the hidden rows: read by matrix products only
     const float* tkv = den_cache_tkv(cache, B2, ntxt);
     const float* ctab = den_cache_ctab(cache, B2, ntxt);               // ntxt > 1: the [9][B2][4][64][64] key^T value matrices
     const int R = B2 + 1;
-    // operand view of a tensor: its S-format twin in the f16x3 path, the fp32 tensor otherwise
-    auto gemm = [&](KrArgs g) { g.split = sp ? 1 : 0; return launch_gemm_kr(g, s); };
-    // combine of S planes of `src` (+ bias, + res), LayerNorm n (or none: RED_PLAIN) -> out / outs; the caller adds what its mode reads
-    auto red = [&](const float* src, int S, const float* bias, const float* res, const NormW* n, float* out, float* outs) {
-        RedArgs r;
-        r.P = src; r.S = S; r.M = M; r.bias = bias; r.res = res; r.out = out; r.outs = outs;
-        if (n != nullptr) { r.mode = RED_LN; r.g = n->g; r.b = n->b; }
-        return r;
+    auto gemm = [&](Twin x, int K, const LinearW& W, Twin y, int ldy, int N, int act = ACT_NONE, const float* res = nullptr) {
+        return launch_gemm_kr(proj_kr(c, x, K, W, y, ldy, N, act, res), s);
     };
 
     // x = cat([sample]*dup) + query_pos.pe[:T]        ladiff.py:472-474, ladiff_denoiser.py:251
     // loop_mode: the caller's step-tail kernel has already written x into P[0] / Ps[0] and will apply encoder.norm itself
-    if (!loop_mode) LADIFF_TRY(launch_add_pe(sample, w.query_pe, Bs, b_lo, b_n, T, P[0], Ps[0], s));
-    const float* cur = P[0]; const float* curs = Ps[0];
+    if (!loop_mode) LADIFF_TRY(launch_add_pe(sample, w.query_pe, Bs, b_lo, b_n, T, P[0].f, P[0].s, s));
+    Twin cur = P[0];
     for (int l = 0; l < NL; ++l) {
-        const DenLayerW& L = w.layer[l];
-        const DenLayerW& Ls = sp ? wsp->layer[l] : w.layer[l];      // matrices as the MFMA reads them
+        const DenLayerW L = mixed(w.layer[l], wm.layer[l]);
+        const LinearW in = in_proj(L.sa_attn), out = out_proj(L.sa_attn);
         const float* tl = tables + (size_t)l * DEN_LAYER_STRIDE;
-        const bool is_in = l < NSKIP, is_out = l > NSKIP;
-        if (is_out) {
-            const LinearW& sk = w.skip[l - NSKIP - 1];
-            const LinearW& sks = sp ? wsp->skip[l - NSKIP - 1] : sk;
-            if (sp) {   // linear_blocks[i](cat(x, skip)): whole 256-wide rows per workgroup, K = 512 streamed (gemm_rowln.hip)
-                RowLnArgs g;
-                g.A = curs; g.lda = D; g.A2 = SKs[NL - 1 - l]; g.lda2 = D; g.K1 = D; g.W = sks.w; g.ldw = 2 * D; g.bias = sk.b;
-                g.Y = P[3]; g.Ys = Ps[3]; g.ldy = D; g.M = M; g.K = 2 * D;
-                LADIFF_TRY(launch_gemm_rowln(g, s));
-            } else {
-                KrArgs g = kr(cur, D, sks.w, nullptr, part, D, M, D, 2 * D);
-                g.A2 = SK[NL - 1 - l]; g.lda2 = D; g.K1 = D;
-                LADIFF_TRY(gemm(g));
-                LADIFF_TRY(launch_reduce_rows(red(part, 2, sk.b, nullptr, nullptr, P[3], Ps[3]), s));
+        if (l > NSKIP) {
+            const LinearW sk = mixed(w.skip[l - NSKIP - 1], wm.skip[l - NSKIP - 1]);
+            // linear_blocks[i](cat(x, skip)); f16x3: whole 256-wide rows per workgroup, K = 512 streamed (gemm_rowln.hip)
+            if (sp) LADIFF_TRY(skip_rowln(c, cur, SK[NL - 1 - l], sk, P[3]));
+            else {
+                LADIFF_TRY(skip_kr(c, cur, SK[NL - 1 - l], sk, part));
+                LADIFF_TRY(launch_reduce_rows(red(c, part, 2, sk.b, nullptr, nullptr, P[3]), s));
             }
-            cur = P[3]; curs = Ps[3];
+            cur = P[3];
         }
-        const float* att_op = att;                    // the attention output as out_proj's operand
+        Twin att_x = operand_only(sp, att);            // the attention output as out_proj's operand
         if (sp && ntxt == 1 && !per_sample) {   // in_proj + attention core in one launch (qkv_attn.hip)
-            LADIFF_TRY(launch_qkv_attention(curs, Ls.sa_attn.in_w, L.sa_attn.in_b, tkv + (size_t)l * B2 * 2 * D, tl,
+            LADIFF_TRY(launch_qkv_attention(cur.s, in.w, in.b, tkv + (size_t)l * B2 * 2 * D, tl,
                                             DEN_OFF_TIME_KV, DEN_STEP_STRIDE, d_step, counts, Bs, b_lo, b_n, T, att, s));
         } else {
-            LADIFF_TRY(gemm(kr(sp ? curs : cur, D, Ls.sa_attn.in_w, L.sa_attn.in_b, qkv, 3 * D, M, 3 * D, D)));
+            LADIFF_TRY(gemm(cur, D, in, Twin{qkv, nullptr}, 3 * D, 3 * D));
             if (ntxt > 1) {
                 // N text tokens as N extra keys (fp32 softmax in both modes); f16x3 mode: the S-format twin of the result goes to
                 // the (still unused) hidden buffer
                 LADIFF_TRY(launch_denoiser_self_attention_general(qkv, tkv + (size_t)l * B2 * ntxt * 2 * D, ntxt, tl, DEN_OFF_TIME_KV,
                                                                   DEN_STEP_STRIDE, d_step, counts, Bs, b_lo, b_n, T, att, s));
-                if (sp) { LADIFF_TRY(launch_split_rows(att, hid, M, D, s)); att_op = hid; }
+                if (sp) { LADIFF_TRY(launch_split_rows(att, hid, M, D, s)); att_x = hid_x; }
             } else      // f16x3 (per-sample step only): written as out_proj's S-format operand
                 LADIFF_TRY(launch_denoiser_self_attention(qkv, tkv + (size_t)l * B2 * 2 * D, tl, DEN_OFF_TIME_KV, DEN_STEP_STRIDE,
                                                           d_step, counts, Bs, b_lo, b_n, T, att, sp ? 1 : 0, s));
         }
         if (sp) {   // X1 = LN1(x + out_proj(att)) -> P[2] / Ps[2], one launch (gemm_rowln.hip)
             RowLnArgs g;
-            g.A = att_op; g.lda = D; g.W = Ls.sa_attn.out_w; g.ldw = D; g.bias = L.sa_attn.out_b; g.res = cur; g.ldres = D;
-            g.ln_g = L.sa_norm1.g; g.ln_b = L.sa_norm1.b; g.Y = P[2]; g.Ys = Ps[2]; g.ldy = D; g.M = M; g.K = D;
+            g.A = att_x.s; g.lda = D; g.W = out.w; g.ldw = D; g.bias = out.b; g.res = cur.f; g.ldres = D;
+            g.ln_g = L.sa_norm1.g; g.ln_b = L.sa_norm1.b; g.Y = P[2].f; g.Ys = P[2].s; g.ldy = D; g.M = M; g.K = D;
             LADIFF_TRY(launch_gemm_rowln(g, s));
         } else {
-            // R1 = x + out_proj(att) -> P[1]
-            KrArgs g = kr(att, D, Ls.sa_attn.out_w, L.sa_attn.out_b, P[1], D, M, D, D);
-            g.res = cur; g.ldres = D;
-            LADIFF_TRY(gemm(g));
-            // X1 = LN1(R1) -> P[2]
-            LADIFF_TRY(launch_reduce_rows(red(P[1], 1, nullptr, nullptr, &L.sa_norm1, P[2], Ps[2]), s));
+            // R1 = x + out_proj(att) -> P[1];  X1 = LN1(R1) -> P[2]
+            LADIFF_TRY(gemm(att_x, D, out, Twin{P[1].f, nullptr}, D, D, ACT_NONE, cur.f));
+            LADIFF_TRY(launch_reduce_rows(red(c, P[1].f, 1, nullptr, nullptr, &L.sa_norm1, P[2]), s));
         }
-        // hid = relu(linear1(X1))
-        {
-            KrArgs g = kr(sp ? Ps[2] : P[2], D, Ls.sa_lin1.w, L.sa_lin1.b, sp ? nullptr : hid, FF, M, FF, D, ACT_RELU);
-            if (sp) g.Ys = hid;
-            LADIFF_TRY(gemm(g));
-        }
-        // X3 = LN2(X1 + linear2(hid)) + c[step, layer, sample] -> P[1]
-        LADIFF_TRY(gemm(kr(hid, FF, Ls.sa_lin2.w, nullptr, part, D, M, D, FF)));
-        const float* x3 = P[1];
+        // hid = relu(linear1(X1));  X3 = LN2(X1 + linear2(hid)) + c[step, layer, sample] -> P[1]
+        LADIFF_TRY(gemm(P[2], D, L.sa_lin1, hid_x, FF, FF, ACT_RELU));
+        LADIFF_TRY(gemm(hid_x, FF, LinearW{L.sa_lin2.w, nullptr}, Twin{part, nullptr}, D, D));
+        Twin x3 = P[1];
         if (ntxt > 1) {
             // literal LinearTemporalCrossAttention (mdiff_transformer.py:219-247): X2 = LN2(..) -> P[1]; q = query(LN(X2));
             // u = SiLU(AdaLN(LN(softmax_d(q) . att_b)));  X3 = X2 + out(u) -> first M x 256 of the qkv buffer
             // f16x3 mode: the two projections run on S-format operands (3 bf16 MFMAs per product), softmax / LayerNorm / AdaLN fp32
-            LADIFF_TRY(launch_reduce_rows(red(part, 4, L.sa_lin2.b, P[2], &L.sa_norm2, P[1], nullptr), s));
-            if (sp) LADIFF_TRY(launch_reduce_rows(red(P[1], 1, nullptr, nullptr, &L.ca_norm, P[2], Ps[2]), s));
-            else LADIFF_TRY(launch_layernorm(P[1], L.ca_norm.g, L.ca_norm.b, P[2], M, s));
-            LADIFF_TRY(gemm(kr(sp ? Ps[2] : P[2], D, Ls.ca_query.w, L.ca_query.b, att, D, M, D, D)));
+            LADIFF_TRY(launch_reduce_rows(red(c, part, 4, L.sa_lin2.b, P[2].f, &L.sa_norm2, Twin{P[1].f, nullptr}), s));
+            if (sp) LADIFF_TRY(launch_reduce_rows(red(c, P[1].f, 1, nullptr, nullptr, &L.ca_norm, P[2]), s));
+            else LADIFF_TRY(launch_layernorm(P[1].f, L.ca_norm.g, L.ca_norm.b, P[2].f, M, s));
+            LADIFF_TRY(gemm(P[2], D, L.ca_query, Twin{att, nullptr}, D, D));
             LADIFF_TRY(launch_lca_apply(att, ctab + (size_t)l * B2 * H * DH * DH, counts, Bs, b_lo, b_n, T, tl + DEN_OFF_CA_MOD,
-                                        DEN_STEP_STRIDE, 0, d_step, L.ca_proj.norm.g, L.ca_proj.norm.b, P[2], s));
-            if (sp) LADIFF_TRY(launch_split_rows(P[2], Ps[2], M, D, s));
-            KrArgs g = kr(sp ? Ps[2] : P[2], D, Ls.ca_proj.out.w, L.ca_proj.out.b, qkv, D, M, D, D);
-            g.res = P[1]; g.ldres = D; g.Ys = sp ? Ps[1] : nullptr;      // X3 (fp32: residual of the ffn block) + its S-format twin (ffn.linear1's operand)
-            LADIFF_TRY(gemm(g));
-            x3 = qkv;
+                                        DEN_STEP_STRIDE, 0, d_step, L.ca_proj.norm.g, L.ca_proj.norm.b, P[2].f, s));
+            if (sp) LADIFF_TRY(launch_split_rows(P[2].f, P[2].s, M, D, s));
+            x3 = Twin{qkv, P[1].s};      // X3 (fp32: residual of the ffn block) + its S-format twin (ffn.linear1's operand)
+            LADIFF_TRY(gemm(P[2], D, L.ca_proj.out, x3, D, D, ACT_NONE, P[1].f));
         } else {
             // the c row of (step, sample | pad): row *d_step - *d_base of [n_steps][B2 + 1], or - per sample - of dctab[b2][valid | pad]
-            RedArgs r = red(part, 4, L.sa_lin2.b, P[2], &L.sa_norm2, P[1], Ps[1]);
+            RedArgs r = red(c, part, 4, L.sa_lin2.b, P[2].f, &L.sa_norm2, P[1]);
             r.mode = RED_LN_ADD; r.counts = counts; r.Bs = Bs; r.T = T; r.b_off = b_lo;
             if (per_sample) { r.tab = dctab + (size_t)l * B2 * 2 * D; r.tab_step_stride = 2 * D; r.pad_row = 1; }
             else { r.tab = ctab + (size_t)l * n_steps * R * D; r.tab_step_stride = R * D; r.pad_row = B2; r.d_step = d_step; r.d_base = d_base; }
             LADIFF_TRY(launch_reduce_rows(r, s, per_sample));
         }
         // u = SiLU(AdaLN(ffn.linear2(gelu(ffn.linear1(X3))))) -> P[2]
-        {
-            KrArgs g = kr(sp ? Ps[1] : x3, D, Ls.ffn1.w, L.ffn1.b, sp ? nullptr : hid, FF, M, FF, D, ACT_GELU);
-            if (sp) g.Ys = hid;
-            LADIFF_TRY(gemm(g));
-        }
-        LADIFF_TRY(gemm(kr(hid, FF, Ls.ffn2.w, nullptr, part, D, M, D, FF)));
-        float* dst = is_in ? SK[l] : P[0];
-        float* dsts = is_in ? SKs[l] : Ps[0];
+        LADIFF_TRY(gemm(x3, D, L.ffn1, hid_x, FF, FF, ACT_GELU));
+        LADIFF_TRY(gemm(hid_x, FF, LinearW{L.ffn2.w, nullptr}, Twin{part, nullptr}, D, D));
+        const Twin dst = l < NSKIP ? SK[l] : P[0];
         if (sp && !per_sample) {   // combine + StylizationBlock + out projection + residual in one launch (gemm_rowln.hip)
             CombineGemmArgs g;
-            g.P = part; g.plane = MD; g.S = 4; g.bias2 = L.ffn2.b; g.ln_g = L.ffn_proj.norm.g; g.ln_b = L.ffn_proj.norm.b;
+            g.P = part; g.plane = (size_t)M * D; g.S = 4; g.bias2 = L.ffn2.b; g.ln_g = L.ffn_proj.norm.g; g.ln_b = L.ffn_proj.norm.b;
             g.tab = tl + DEN_OFF_FFN_MOD; g.tab_step_stride = DEN_STEP_STRIDE; g.d_step = d_step;
-            g.W = Ls.ffn_proj.out.w; g.ldw = D; g.bias = L.ffn_proj.out.b; g.res = x3; g.ldres = D;
-            g.Y = dst; g.Ys = dsts; g.ldy = D; g.M = M;
+            g.W = L.ffn_proj.out.w; g.ldw = D; g.bias = L.ffn_proj.out.b; g.res = x3.f; g.ldres = D;
+            g.Y = dst.f; g.Ys = dst.s; g.ldy = D; g.M = M;
             LADIFF_TRY(launch_combine_gemm(g, s));
         } else {
             // (scale | shift) of row *d_step, or - per sample - of row b2
-            RedArgs r = red(part, 4, L.ffn2.b, nullptr, &L.ffn_proj.norm, P[2], Ps[2]);
+            RedArgs r = red(c, part, 4, L.ffn2.b, nullptr, &L.ffn_proj.norm, P[2]);
             r.mode = RED_LN_MOD; r.tab = tl + DEN_OFF_FFN_MOD; r.tab_step_stride = DEN_STEP_STRIDE; r.d_step = d_step;
             if (per_sample) { r.T = T; r.b_off = b_lo; }
             LADIFF_TRY(launch_reduce_rows(r, s, per_sample));
-            // x' = X3 + out_layers(u)
-            KrArgs g = kr(sp ? Ps[2] : P[2], D, Ls.ffn_proj.out.w, L.ffn_proj.out.b, dst, D, M, D, D);
-            g.res = x3; g.ldres = D; g.Ys = dsts;
-            LADIFF_TRY(gemm(g));
+            LADIFF_TRY(gemm(P[2], D, L.ffn_proj.out, dst, D, D, ACT_NONE, x3.f));      // x' = X3 + out_layers(u)
         }
-        cur = dst; curs = dsts;
+        cur = dst;
     }
     // encoder.norm, then [B2,T,256] out   cross_attention.py:84-85, ladiff_denoiser.py:272,292
     if (loop_mode) return 0;          // left in P[0] for launch_step_tail
-    return launch_layernorm(cur, w.norm.g, w.norm.b, eps, M, s);
+    return launch_layernorm(cur.f, w.norm.g, w.norm.b, eps, M, s);
 }
 
 }  // namespace ladiff

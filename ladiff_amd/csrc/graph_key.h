@@ -139,6 +139,20 @@ struct DecSwitches {              // one reading of the decoder's measurement sw
     int fused_attn;               // (+ 16 clears it, + 32 = always): in_proj inside the attention kernel, else GEMM + attention kernel as two launches (the path before)
     int mlp_variant;              // ladiff_debug_set_mlp_variant: workgroup form of the fused feed-forward kernel
 };
+// Which launches a decode makes (decoder.hip), decided once per call; vae_decode branches on nothing else.  small: the GEMMs on the small-M
+// kernels; fused_attn: in_proj inside the attention kernel; out_cross: out_proj .. norm2 in one kernel (never on the small route); fused_mlp: the
+// feed-forward block in one kernel; final_split: final_layer on padded f16x3 tiles.  All false in fp32 mode (truth table: tests/graph_key_check.cpp).
+constexpr int DEC_SMALL_ROWS = 4096;
+struct DecRoute { bool small, fused_attn, out_cross, fused_mlp, final_split; };
+inline DecRoute dec_route(bool split_mode, int rows, const DecSwitches& sw, int mlp_min_rows) {
+    DecRoute r;
+    r.small = split_mode && rows < DEC_SMALL_ROWS && sw.small_rows_path;
+    r.fused_attn = split_mode && sw.fused_attn && (rows >= DEC_SMALL_ROWS || sw.fused_attn == 2);
+    r.out_cross = split_mode && !r.small && sw.out_cross;
+    r.fused_mlp = split_mode && sw.fused_mlp && (rows >= mlp_min_rows || sw.fused_mlp == 2);
+    r.final_split = split_mode && rows >= DEC_SMALL_ROWS && sw.final_split;
+    return r;
+}
 // Key of a decode graph (ladiff_vae_decode_graphed): EVERY field of the call's switch snapshot is part of it.
 inline GraphKey decode_key(const float* const* w, const float* const* w_split, int n_params, uint64_t weights_generation, const float* z,
                            const int32_t* lengths, const int32_t* counts, const int32_t* row_off, int total_rows, int B, int F, int T, int C,

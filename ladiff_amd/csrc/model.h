@@ -2,27 +2,12 @@
 // size queries (*_ws_floats, *_floats, den_cache_*, den_loop_io, carve_reverse), is workspace.h's: one layout per workspace.
 #pragma once
 #include <atomic>
-#include "gemm.h"
-#include "gemm_kr.h"
 #include "graph_key.h"
-#include "kernels.h"
+#include "seq.h"             // gemm.h, gemm_kr.h, kernels.h, weights.h; lin / kr, the pair type and the builders the sequencers share
 #include "systolic_plan.h"
-#include "weights.h"
 #include "workspace.h"
 
 namespace ladiff {
-
-// argument builders of the two small-GEMM launchers: one dense [N][K] weight, activations with their own row strides
-inline GemmArgs lin(const float* A, int lda, const LinearW& l, float* Y, int ldy, int M, int N, int K, int act = ACT_NONE) {
-    GemmArgs g;
-    g.A = A; g.lda = lda; g.W = l.w; g.ldw = K; g.bias = l.b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
-    return g;
-}
-inline KrArgs kr(const float* A, int lda, const float* W, const float* b, float* Y, int ldy, int M, int N, int K, int act = ACT_NONE) {
-    KrArgs g;
-    g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = b; g.Y = Y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.act = act;
-    return g;
-}
 
 int denoiser_time_tables(const DenoiserW& w, const float* sinus, int n, float* tables, float* ws, size_t ws_floats, hipStream_t s);
 int denoiser_text_cache(const DenoiserW& w, const float* text, int B2, const float* tables, int n_steps, float* cache,

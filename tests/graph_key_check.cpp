@@ -127,6 +127,38 @@ int main() {
         CHECK(key_of(a0) != key_of(a1) && key_of(a0) == key_of(a0) && key_of(a1) == key_of(a1));
     }
     CHECK(dkey(-1, 0) != sampler_key(a, 3, true, 1, 6, off));
+
+    // dec_route: which launches a decode makes, decided once from (mode, rows, switches).  The rule restated: nothing is routed in fp32
+    // mode; the small-M GEMMs below 4,096 rows if switched on; in_proj inside the attention kernel from 4,096 rows or always (2);
+    // out_proj + cross-attention in one kernel only on the large-M side; the fused feed-forward from mlp_min_rows or always (2);
+    // final_layer on padded tiles from 4,096 rows.
+    int routes = 0;
+    for (bool split_mode : {false, true})
+        for (int rows : {1, 4095, 4096, 9999, 10000})
+            for (int fused_mlp : {0, 1, 2})
+                for (int small_rows_path : {0, 1})
+                    for (int final_split : {0, 1})
+                        for (int out_cross : {0, 1})
+                            for (int fused_attn : {0, 1, 2}) {
+                                const DecSwitches sw{fused_mlp, small_rows_path, final_split, out_cross, fused_attn, 0};
+                                const DecRoute r = dec_route(split_mode, rows, sw, 10000);
+                                const bool big = rows >= 4096;
+                                const bool small = split_mode && !big && small_rows_path == 1;
+                                CHECK(r.small == small);
+                                CHECK(r.fused_attn == (split_mode && (fused_attn == 2 || (fused_attn == 1 && big))));
+                                CHECK(r.out_cross == (split_mode && !small && out_cross == 1));
+                                CHECK(r.fused_mlp == (split_mode && (fused_mlp == 2 || (fused_mlp == 1 && rows >= 10000))));
+                                CHECK(r.final_split == (split_mode && big && final_split == 1));
+                                if (!split_mode) CHECK(!r.small && !r.fused_attn && !r.out_cross && !r.fused_mlp && !r.final_split);
+                                CHECK(!(r.out_cross && r.small));
+                                ++routes;
+                            }
+    CHECK(routes == 720);
+    CHECK(DEC_SMALL_ROWS == 4096);
+    {   // the threshold of the fused feed-forward is the caller's argument, not a constant of the rule
+        const DecSwitches sw{1, 1, 1, 1, 1, 0};
+        CHECK(dec_route(true, 5000, sw, 5000).fused_mlp && !dec_route(true, 4999, sw, 5000).fused_mlp);
+    }
     std::printf("graph_key_check: ok\n");
     return 0;
 }
