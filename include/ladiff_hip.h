@@ -635,6 +635,30 @@ LADIFF_API int ladiff_t2m_text_encode(const float* const* w, const float* word_e
 LADIFF_API int ladiff_feats2joints(const float* feats, const float* mean, const float* std, int B, int F, int C, int njoints,
                         float* joints, ladiff_stream_t stream);
 
+/* ------------------------------------------------------------------ joints2feats (csrc/joints2feats.hip)
+ * The inverse direction: feats[B,L-1,263] = process_file(joints[b, :h_lengths[b]], feet_thre)[0] per motion - what
+ * HumanML3DDataModule.joints2feats is meant to call (data/HumanML3D.py:50-55; data/humanml/scripts/motion_process.py:169-351 with
+ * uniform_skeleton :13-36, common/skeleton.py:43-147, common/quaternion.py, scipy's gaussian_filter1d(., 20, mode='nearest')).
+ * joints [B,L,22,3] fp32, 2 <= h_lengths[b] <= L <= 256 (h_lengths: HOST int32 [B]; the counts travel in the kernel arguments, so
+ * the entry neither copies, allocates nor synchronises; one launch per 1024 motions; no workspace).  Motion b fills rows
+ * 0 .. h_lengths[b]-2 of feats[b]; every later row is written as zeros, as ladiff_vae_decode leaves padding.
+ *   target_offsets  device [22,3] = Skeleton.get_offsets_joints of the target pose: the motion is first retargeted to that skeleton
+ *                   (per-frame inverse kinematics, forward kinematics with these offsets, root scaled by the leg-length ratio of
+ *                   frame 0).  NULL skips the step: the mode for motions already on the model's skeleton (ladiff_feats2joints output).
+ *   feet_thre       a foot contact is set where the squared displacement of joints 7, 10 (left) and 8, 11 (right) to the next frame
+ *                   is < feet_thre; the reference's data scripts use 0.002 for HumanML3D (motion_process.py:468).  NOT
+ *                   HumanML3D.py:51, which passes njoints in this place.
+ *   mean, std       device [263], both or neither: (x - mean) / std fused into the store (rows of padding stay zero).
+ * Arithmetic is fp32 in every build flavour.  Kept from the reference: inverse_kinematics_np unpacks the face joints [2,1,17,16] as
+ * l_hip, r_hip, ... where process_file unpacks r_hip, l_hip, ... (the per-frame forward vector comes from the DIFFERENCE of shoulder
+ * and hip span, the initial facing from their sum); qbetween has no anti-parallel case; qbetween's torch.cross has no dim, so a motion
+ * of exactly 3 frames takes its cross products along the frame axis; frame 0's root rotation is the identity.
+ * Errors, all before any GPU work: njoints != 22 -> LADIFF_ERR_UNSUPPORTED (KIT is not built); LADIFF_ERR_ARG for B < 0, a NULL
+ * joints / h_lengths / feats, feet_thre <= 0 or exactly one of mean / std NULL; LADIFF_ERR_SHAPE for L outside [2, 256], a length
+ * outside [2, L] or a pointer not aligned to 4 bytes.  B == 0 does nothing. */
+LADIFF_API int ladiff_joints2feats(const float* joints, const int32_t* h_lengths, int B, int L, int njoints, const float* target_offsets,
+                        float feet_thre, const float* mean, const float* std, float* feats, ladiff_stream_t stream);
+
 /* ------------------------------------------------------------------ joint-space metrics (csrc/joint_metrics.hip)
  * The reference's ComputeMetrics ("TemosMetric": APE / AVE, models/metrics/compute.py:102-196) and MRMetrics (MPJPE / PA-MPJPE /
  * ACCEL, models/metrics/mr.py:73-96) on joints_rst / joints_ref [B,F,J,3] as ladiff_feats2joints leaves them (call sites

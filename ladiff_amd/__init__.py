@@ -4,6 +4,7 @@ Host side (this package): parameter containers with the reference's state-dict s
 the `LADIFF`-compatible loop owner.  Arithmetic: libladiff_hip.so (ladiff_amd/csrc, C ABI in include/ladiff_hip.h).
 """
 from .feats2joints import Feats2Joints                   # noqa: F401
+from .joints2feats import Joints2Feats                   # noqa: F401
 from .modules import LADiffDenoiser, LADiffVae          # noqa: F401
 from .pipeline import LADIFF, instantiate_from_config   # noqa: F401
 from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler    # noqa: F401

@@ -716,6 +716,18 @@ int ladiff_feats2joints(const float* feats, const float* mean, const float* std,
     return launch_feats2joints(feats, mean, std, B, F, C, njoints, joints, S(stream));
 }
 
+// ------------------------------------------------------------------ joints2feats (csrc/joints2feats.hip)
+int ladiff_joints2feats(const float* joints, const int32_t* h_lengths, int B, int L, int njoints, const float* target_offsets, float feet_thre,
+                        const float* mean, const float* std, float* feats, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(B >= 0);
+    if (njoints != 22) return LADIFF_ERR_UNSUPPORTED;            // the reference has joints2feats for HumanML3D only
+    if (B == 0) return 0;
+    LADIFF_CHECK_ARG(joints && h_lengths && feats && feet_thre > 0.f && (mean == nullptr) == (std == nullptr));
+    for (const void* p : {(const void*)joints, (const void*)target_offsets, (const void*)mean, (const void*)std, (const void*)feats})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return LADIFF_ERR_SHAPE;
+    return launch_joints2feats(joints, h_lengths, B, L, target_offsets, feet_thre, mean, std, feats, S(stream));
+}
+
 // ------------------------------------------------------------------ joint-space metrics (csrc/joint_metrics.hip)
 namespace {
 // what both entries check on the host before anything is launched

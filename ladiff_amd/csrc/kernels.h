@@ -109,6 +109,10 @@ int launch_decoder_cross_apply(const float* x, const float* bo, const float* g2,
 int launch_feats2joints(const float* feats, const float* mean, const float* stdv, int B, int F, int C, int J, float* joints,
                         hipStream_t s);
 
+// joints2feats.hip: h_lengths is the HOST array of frame counts (they travel in the kernel arguments)
+int launch_joints2feats(const float* joints, const int32_t* h_lengths, int B, int L, const float* tgt, float feet_thre, const float* mean,
+                        const float* stdv, float* feats, hipStream_t s);
+
 // joint_metrics.hip: one row of sums per sequence, then the rows added to acc in fp64 in sequence order
 int launch_joint_ape_ave(const float* rst, const float* ref, const int32_t* lengths, int B, int F, int J, const int32_t* part_idx,
                          float factor, float* seq_rows, double* acc, hipStream_t s);

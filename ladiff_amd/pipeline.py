@@ -28,6 +28,7 @@ from torch import nn
 
 from . import _lib
 from .feats2joints import Feats2Joints
+from .joints2feats import Joints2Feats
 from .schedulers import DDIMScheduler, DDPMScheduler, timestep_sinusoid
 
 _TARGET_ALIASES = {
@@ -125,6 +126,8 @@ class LADIFF(nn.Module):
         self.feats2joints = getattr(datamodule, "feats2joints", None)      # the reference's CPU function (HumanML3D.py:44-48)
         # same arithmetic on the GPU when the datamodule exposes mean / std / njoints; joints then cross PCIe, not features
         self.feats2joints_device = Feats2Joints.from_datamodule(datamodule) if datamodule is not None else None
+        # the other direction (HumanML3D only): joints - `forward`'s own result, a mocap clip - to the features `edit` and `vae.encode` take
+        self.joints2feats_device = Joints2Feats.from_datamodule(datamodule) if datamodule is not None else None
         self.sample_mean = False
         self.fact = None
         self.times = []
@@ -788,20 +791,27 @@ class LADIFF(nn.Module):
         per prompt, `scheduler.start_step`) and denoised from there under `batch["text"]`.  `batch["length"]` are the TARGET lengths (the
         valid mask of the loop and of the decode); the source is `batch["motion"]` (features as `recon_from_motion` takes them, of
         `batch["source_length"]` frames, default the target's) through `vae.encode` - its sample, drawn as `recon_from_motion` draws it, or
-        with `eps` - or `latents=` [T,B,256], e.g. the z of an earlier `sample`.  Rows of the source past its own latent count are zeros,
-        as `encode` leaves them.  Returns what `forward` returns."""
+        with `eps` - or `batch["joints"]` (joint positions as `forward` returns them: a padded [B,L,22,3] tensor with
+        `batch["source_length"]` JOINT frames per prompt, default L, or a list of [L_b,22,3]; `joints2feats_device(normalize=True)` turns
+        them into L_b - 1 feature frames, which then go the way of `motion`) - or `latents=` [T,B,256], e.g. the z of an earlier
+        `sample`.  Rows of the source past its own latent count are zeros, as `encode` leaves them.  Returns what `forward` returns."""
         texts, lengths = batch["text"], [int(l) for l in batch["length"]]
         if self.text_encoder is None or (self.feats2joints is None and self.feats2joints_device is None):
             raise RuntimeError("LADIFF.edit needs a text_encoder callable and datamodule.feats2joints")
-        if (latents is None) == (batch.get("motion") is None):
-            raise ValueError('LADIFF.edit takes exactly one source: batch["motion"] or latents=')
+        if (latents is not None) + (batch.get("motion") is not None) + (batch.get("joints") is not None) != 1:
+            raise ValueError('LADIFF.edit takes exactly one source: batch["motion"], batch["joints"] or latents=')
         starts = self._start_steps(len(lengths), strength, None)         # argument errors before any GPU work
+        joints_src = self._joints_source(batch, len(lengths)) if batch.get("joints") is not None else None
         self._check_loaded_weights()
         start = time.time()
         with torch.no_grad():
             if latents is None:
-                src_len = [int(l) for l in batch.get("source_length", lengths)]
-                latents, _, _ = self.vae.encode(batch["motion"].detach().to(self.device), src_len, **({} if eps is None else {"eps": eps}))
+                if joints_src is not None:
+                    motion = self.joints2feats_device(joints_src[0].detach().to(self.device), joints_src[1], normalize=True)
+                    src_len = [l - 1 for l in joints_src[1]]
+                else:
+                    motion, src_len = batch["motion"].detach().to(self.device), [int(l) for l in batch.get("source_length", lengths)]
+                latents, _, _ = self.vae.encode(motion, src_len, **({} if eps is None else {"eps": eps}))
             text_emb = self.text_encoder(self._guided_texts(texts))
             z = self._diffusion_reverse(text_emb, lengths, guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index,
                                         source_latents=latents.to(self.device, torch.float32), start_steps=starts)
@@ -813,11 +823,38 @@ class LADIFF(nn.Module):
         self.times.append(time.time() - start)
         return remove_padding(joints.cpu(), lengths)
 
+    def _joints_source(self, batch, n_prompts):
+        """`batch["joints"]` as (padded [B,L,22,3] tensor, joint frames per prompt); every argument error of the joints source, host only."""
+        if self.joints2feats_device is None:
+            raise RuntimeError('batch["joints"] needs a HumanML3D datamodule with mean / std (joints2feats_device)')
+        joints = batch["joints"]
+        if isinstance(joints, (list, tuple)):
+            if any(not torch.is_tensor(j) or j.dim() != 3 for j in joints) or len(joints) == 0:
+                raise ValueError('batch["joints"] as a list holds one [L_b, 22, 3] tensor per prompt')
+            frames = [int(j.shape[0]) for j in joints]
+            padded = joints[0].new_zeros((len(joints), max(frames)) + tuple(joints[0].shape[1:]))
+            for b, j in enumerate(joints):
+                if j.shape[1:] != joints[0].shape[1:]:
+                    raise ValueError('batch["joints"] as a list holds one [L_b, 22, 3] tensor per prompt')
+                padded[b, :frames[b]] = j
+            joints = padded
+        else:
+            if not torch.is_tensor(joints) or joints.dim() != 4:
+                raise ValueError('batch["joints"] is a padded [B, L, 22, 3] tensor or a list of [L_b, 22, 3]')
+            frames = [int(l) for l in batch.get("source_length", [joints.shape[1]] * joints.shape[0])]
+        if joints.shape[0] != n_prompts:
+            raise ValueError(f"{joints.shape[0]} joint sources for {n_prompts} prompts")
+        _, L, frames = self.joints2feats_device.check(joints.shape, frames, normalize=True)
+        if L - 1 + 2 * self.vae.max_it > _lib.MAX_FRAMES:                # vae.encode's own limit, on the L - 1 feature frames
+            raise NotImplementedError(f"encode handles up to {_lib.MAX_FRAMES - 2 * self.vae.max_it} frames: a joints source of at most "
+                                      f"{_lib.MAX_FRAMES - 2 * self.vae.max_it + 1} frames, got {L}")
+        return joints, frames
+
     demo_strength = None      # `forward_motion_style_transfer`: the strength of the demo's edit (a loop owner sets it from its config), default 0.6
 
     def forward_motion_style_transfer(self, batch):
-        """The name the reference's demo.py:182 calls (its own LADIFF class has no such method).  Here: `edit` of `batch["motion"]`
-        under `batch["text"]` - SDEdit, not MLD's three-branch guidance."""
+        """The name the reference's demo.py:182 calls (its own LADIFF class has no such method).  Here: `edit` of `batch["motion"]` (or
+        of `batch["joints"]`, as `edit` takes them) under `batch["text"]` - SDEdit, not MLD's three-branch guidance."""
         return self.edit(batch, strength=self.demo_strength or 0.6)
 
     def _guided_texts(self, texts):
