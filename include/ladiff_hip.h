@@ -475,6 +475,23 @@ LADIFF_API int ladiff_vae_decode_ragged(const float* const* w, const float* cons
                              const int32_t* lengths, const int32_t* counts, const int32_t* row_off, int total_rows, int B,
                              int F, int T, int C, float* feats, void* ws, size_t ws_bytes, ladiff_stream_t stream);
 
+/* The same decode (padded rows when row_off == NULL - total_rows is then not read -, ragged otherwise) that ALSO returns the decoder's
+ * cross-attention weights, frames against latents, of every layer: the `plot_att_map` analysis of the reference
+ * (cross_attention.py:113-148, :373-406).  att_maps is dense float32 [9][B][F][T], layers in execution order (input_blocks.0..3,
+ * middle_block, output_blocks.0..3):
+ *   att_maps[l][b][f][j] = (1/4) sum_h softmax_j(q_h[b,f] . k_h[b,j] / 8),  the head-averaged weights nn.MultiheadAttention returns,
+ * taken from the decode's own folded scores (fp32 in both modes), so they describe what this decode computed.  Tokens j >= counts[b]
+ * are masked before the softmax and written as exactly 0.0f; counts == NULL masks no token.  Frames f >= lengths[b] are written as
+ * zeros, as in feats (the reference computes weights for padded frames too).  Every word of att_maps and feats is written: nothing
+ * depends on what they held.  The fused out_proj + cross-attention kernel of the f16x3 large-row route never forms the rows the
+ * weights are taken from, so this call runs that step as its two launches (ladiff_debug_set_decoder_fusion(1 + 64) gives the same
+ * feats); nine launches more than a decode, and never captured into a graph.  The workspace of
+ * ladiff_decoder_workspace_bytes(B, F, T, C) is enough.  Argument, shape and workspace errors return before anything is queued. */
+LADIFF_API int ladiff_vae_decode_att_maps(const float* const* w, const float* const* w_split /*or NULL*/, const float* z,
+                             const int32_t* lengths, const int32_t* counts /*or NULL*/, const int32_t* row_off /*or NULL: padded rows*/,
+                             int total_rows, int B, int F, int T, int C, float* feats, float* att_maps /*[9,B,F,T]*/, void* ws,
+                             size_t ws_bytes, ladiff_stream_t stream);
+
 /* The same decode (padded when row_off == NULL, ragged otherwise) captured into a hipGraph on first use and replayed: for batches
  * of few frame rows, where the ~110 launches of a decode are a few microseconds each and the host's launch rate, not the GPU, sets
  * the time (config c1: 8 motions x 60 frames).  `graph` comes from ladiff_decoder_graph_create; the graph is keyed on every pointer

@@ -185,6 +185,8 @@ _SIGNATURES = {
                                           c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "ladiff_vae_decode_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                          c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ladiff_vae_decode_att_maps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                           c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -851,4 +851,23 @@ int ladiff_vae_decode_ragged(const float* const* w, const float* const* w_split,
                       ws_bytes / sizeof(float), S(stream), g_dec.snapshot());
 }
 
+// the decode (padded when row_off == NULL, ragged otherwise) that also returns every layer's cross-attention weights; never captured
+int ladiff_vae_decode_att_maps(const float* const* w, const float* const* w_split, const float* z, const int32_t* lengths,
+                               const int32_t* counts, const int32_t* row_off, int total_rows, int B, int F, int T, int C, float* feats,
+                               float* att_maps, void* ws, size_t ws_bytes, ladiff_stream_t stream) {
+    DecoderW W, WS;
+    LADIFF_CHECK_ARG(load_weights(W, w) && z && lengths && feats && att_maps && ws && B >= 0 && total_rows >= 0);
+    if (w_split != nullptr) LADIFF_CHECK_ARG(load_weights(WS, w_split));
+    if (F < 1 || F > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;
+    if (row_off != nullptr && (size_t)total_rows > (size_t)B * F) return LADIFF_ERR_SHAPE;
+    if (ws_bytes < ladiff_decoder_workspace_bytes(B, F, T, C)) return LADIFF_ERR_WORKSPACE;
+    if (B == 0) return 0;
+    if (row_off != nullptr) {
+        LADIFF_HIP(hipMemsetAsync(feats, 0, (size_t)B * F * C * sizeof(float), S(stream)));      // as ladiff_vae_decode_ragged
+        if (total_rows == 0) LADIFF_HIP(hipMemsetAsync(att_maps, 0, (size_t)NL * B * F * T * sizeof(float), S(stream)));      // no row, no launch
+    }
+    return vae_decode(W, w_split ? &WS : nullptr, z, lengths, counts, row_off, row_off ? total_rows : 0, B, F, T, C, feats, (float*)ws,
+                      ws_bytes / sizeof(float), S(stream), g_dec.snapshot(), att_maps);
+}
+
 }  // extern "C"

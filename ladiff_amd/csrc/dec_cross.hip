@@ -655,4 +655,149 @@ int launch_decoder_out_cross(const float* att_s, const float* x0, const float* w
     return 0;
 }
 
+// ---------------------------------------------------------------- the cross-attention weights themselves (an analysis call: plot_att_map)
+//   maps[b, f, j] = (1/4) sum_h softmax_j( x1n[b,f] . G[b,h,j] + c[b,h,j] )        cross_attention.py:373-406 (head-averaged weights)
+// The probabilities of cross_row, kept instead of applied: the same rows (norm1 on load when g1 / b1 are given), the same folded keys
+// (1 / 8 inside G), the same fmaf chains, 16-lane sums and exp2 softmax, so a map holds what the decode of these rows multiplied U
+// by.  U is not needed: the sample's G is copied compactly ([H][T][256], half of apply's LDS).  Grid (B, chunks) over the F frames of the
+// PADDED output layout; a sample's own frames are rows row0 .. row0 + flen - 1 (flen = lengths[b]; ragged: its row_off span), every
+// later frame and every token >= counts[b] is written as 0.0f.  A pass is 16 frame rows = 16 T consecutive floats of [b][f][:]: they are
+// staged in LDS (two buffers: one barrier per pass) and leave as whole 16-byte words, scalar stores only up to the first aligned word
+// and behind the last.
+template <int TT>
+__global__ __launch_bounds__(256) void dec_cross_maps_kernel(const float* __restrict__ x, const float* __restrict__ gu,
+                                                             const float* __restrict__ cc, const int32_t* __restrict__ counts,
+                                                             const int32_t* __restrict__ lengths, const int32_t* __restrict__ row_off,
+                                                             const float* __restrict__ g1, const float* __restrict__ b1, int F,
+                                                             int rows_per_wg, float* __restrict__ maps) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];                    // G [H][TT][256], then c [H][TT], then 2 x [16][TT] staging
+    constexpr int T = TT, HT = H * TT;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* cs = sm + (size_t)HT * D;
+    float* stg = cs + HT;
+    size_t row0 = (size_t)b * F;
+    int flen = lengths[b];
+    if (row_off != nullptr) { row0 = row_off[b]; flen = row_off[b + 1] - row_off[b]; }
+    flen = flen < F ? flen : F;
+    const int f0 = blockIdx.y * rows_per_wg;
+    const int f1 = f0 + rows_per_wg < F ? f0 + rows_per_wg : F;
+    if (f0 < flen) {                                                              // uniform over the workgroup
+        const float* src = gu + (size_t)b * HT * 2 * D;
+        for (int u = tid; u < HT * D / 4; u += 256) {
+            const int hj = u / (D / 4), c4 = u - hj * (D / 4);
+            st4(sm + 4 * u, ld4(src + (size_t)hj * 2 * D + 4 * c4));
+        }
+        if (tid < HT) cs[tid] = cc[(size_t)b * HT + tid];
+    }
+    int nv = counts != nullptr ? counts[b] : T;
+    nv = nv > T ? T : nv;
+    __syncthreads();
+    const int l16 = lane & 15, grp = lane >> 4, c0 = 4 * l16, lr = 4 * wave + grp;
+    int pass = 0;
+    for (int fb = f0; fb < f1; fb += 16, ++pass) {
+        const int f = fb + lr;
+        float mp[T];
+#pragma unroll
+        for (int j = 0; j < T; ++j) mp[j] = 0.f;
+        if (fb < flen) {                                                          // uniform: the pass has a frame of the sample
+            const size_t row = row0 + (f < flen ? f : flen - 1);
+            f32x4 xv[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) xv[k] = ld4(x + row * D + c0 + 64 * k);
+            if (g1 != nullptr) {                                                  // norm1 on load, as dec_cross_apply_kernel
+                float s1 = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) s1 += (xv[k][0] + xv[k][1]) + (xv[k][2] + xv[k][3]);
+                const float mean1 = row16_sum(s1) * (1.f / 256.f);
+                float q1 = 0.f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { const float dlt = xv[k][i] - mean1; q1 += dlt * dlt; }
+                const float rstd1 = rsqrtf(row16_sum(q1) * (1.f / 256.f) + LN_EPS);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const f32x4 ga = ld4(g1 + c0 + 64 * k), be = ld4(b1 + c0 + 64 * k);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) xv[k][i] = (xv[k][i] - mean1) * rstd1 * ga[i] + be[i];
+                }
+            }
+#pragma unroll 1
+            for (int h = 0; h < H; ++h) {                                         // cross_row's scores and softmax, head by head
+                float sc[T];
+#pragma unroll
+                for (int j = 0; j < T; ++j) {
+                    const float* gp = sm + (size_t)(h * T + j) * D + c0;
+                    float d = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const f32x4 g4 = ld4(gp + 64 * k);
+                        d = fmaf(xv[k][0], g4[0], fmaf(xv[k][1], g4[1], fmaf(xv[k][2], g4[2], fmaf(xv[k][3], g4[3], d))));
+                    }
+                    sc[j] = d;
+                }
+#pragma unroll
+                for (int j = 0; j < T; ++j) sc[j] = row16_sum(sc[j]) + cs[h * T + j];
+                float m = -INFINITY;
+#pragma unroll
+                for (int j = 0; j < T; ++j) { sc[j] = j < nv ? sc[j] : -INFINITY; m = fmaxf(m, sc[j]); }
+                float l = 0.f;
+#pragma unroll
+                for (int j = 0; j < T; ++j) { sc[j] = __builtin_amdgcn_exp2f((sc[j] - m) * 1.4426950408889634f); l += sc[j]; }
+                const float inv = 1.f / l;
+#pragma unroll
+                for (int j = 0; j < T; ++j) mp[j] += sc[j] * inv;                 // a masked token: exp2(-inf) = 0, stays 0.0f
+            }
+        }
+        float* sb = stg + (pass & 1) * 16 * T;
+        const bool live = f < flen;                                               // frames past the length: zeros, as feats
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+            if (l16 == j) sb[lr * T + j] = live ? mp[j] * (1.f / H) : 0.f;
+        __syncthreads();
+        // frames fb .. fb + nr - 1 of the sample: n consecutive floats from maps[(b F + fb) T]
+        const int nr = f1 - fb < 16 ? f1 - fb : 16, n = nr * T;
+        float* dst = maps + ((size_t)b * F + fb) * T;
+        int lead = (int)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) >> 2;   // floats in front of the first 16-byte word
+        lead = lead < n ? lead : n;
+        const int words = (n - lead) >> 2, tail = n - lead - 4 * words;
+        if (tid < words) {
+            const float* s4 = sb + lead + 4 * tid;
+            st4(dst + lead + 4 * tid, f32x4{s4[0], s4[1], s4[2], s4[3]});
+        } else if (tid >= 32 && tid < 32 + lead) {
+            dst[tid - 32] = sb[tid - 32];
+        } else if (tid >= 36 && tid < 36 + tail) {
+            dst[lead + 4 * words + tid - 36] = sb[lead + 4 * words + tid - 36];
+        }
+    }
+}
+
+// maps [B][F][T] of one layer from the inputs of launch_decoder_cross_apply for that layer (x: the rows it reads; g1 / b1 as there)
+int launch_decoder_cross_maps(const float* x, const int32_t* counts, const int32_t* lengths, int B, int F, int T, const float* gu_ws,
+                              float* maps, hipStream_t s, const int32_t* row_off, const float* g1, const float* b1) {
+    if (B == 0 || F == 0) return 0;
+    if (T < 1 || T > TM) return LADIFF_ERR_SHAPE;
+    const float* gu = gu_ws;
+    const float* cc = gu_ws + (size_t)B * H * T * 2 * D;
+    int chunks = (512 + B - 1) / B;                                                // as cross_apply: the chip covered twice
+    if (chunks > (F + 15) / 16) chunks = (F + 15) / 16;
+    if (chunks < 1) chunks = 1;
+    const int rows_per_wg = ((F + chunks - 1) / chunks + 15) / 16 * 16;
+    chunks = (F + rows_per_wg - 1) / rows_per_wg;
+    const size_t lds = ((size_t)H * T * D + H * T + 2 * 16 * T) * sizeof(float);  // 33.6 KiB at T = 8: below the default limit
+#define LADIFF_DM_CASE(TT)                                                                                                      \
+    case TT:                                                                                                                    \
+        hipLaunchKernelGGL(dec_cross_maps_kernel<TT>, dim3(B, chunks), dim3(256), lds, s, x, gu, cc, counts, lengths, row_off, \
+                           g1, b1, F, rows_per_wg, maps);                                                                      \
+        break;
+    switch (T) {
+        LADIFF_DM_CASE(1) LADIFF_DM_CASE(2) LADIFF_DM_CASE(3) LADIFF_DM_CASE(4)
+        LADIFF_DM_CASE(5) LADIFF_DM_CASE(6) LADIFF_DM_CASE(7) LADIFF_DM_CASE(8)
+        default: return LADIFF_ERR_SHAPE;
+    }
+#undef LADIFF_DM_CASE
+    LADIFF_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace ladiff

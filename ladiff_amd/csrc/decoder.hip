@@ -35,8 +35,11 @@ DecSwitchAtoms g_dec;                          // the measurement switches (mode
 //   skip concat first (gemm; small: gemm_rowln).  Switches - small_rows_path 0: the large-M forms at any row count;  fused_attn 0: in_proj gemm +
 //   self-attention (split), 2: dec_qkv_attn below 4,096 rows too;  out_cross 0: out_proj gemm + cross_apply;  fused_mlp 0: never dec_mlp, 2: always;
 //   final_split 0: final_layer on the fp32 gemm as in fp32 mode, else pad_rows + gemm + scatter_feats
+// att_maps != nullptr ([NL][B][F][T], layers in execution order): out_cross off for this call, and cross_maps (+ 1 per layer) between the
+//   out_proj gemm and cross_apply.  A call without it makes the launches above.
 int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int32_t* lengths, const int32_t* counts,
-               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s, const DecSwitches& sw) {
+               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s, const DecSwitches& sw,
+               float* att_maps) {
     if (F < 1 || F > LADIFF_MAX_FRAMES || T < 1 || T > LADIFF_MAX_LATENTS || C < 1) return LADIFF_ERR_SHAPE;
     const bool ragged = row_off != nullptr;
     if (ragged && (R < 0 || (size_t)R > (size_t)B * F)) return LADIFF_ERR_SHAPE;
@@ -57,7 +60,11 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
     // that the LayerNorm row pass sums) - the same S-format operands and products, 3 - 4x the workgroups.  From DEC_SMALL_ROWS up in_proj
     // runs inside the attention kernel (dec_qkv_attn.hip; 8 x 60 frames: 0.47 ms against 0.45 with the small-M in_proj + attention
     // launches; 128 x 196: 2.28 against 2.41, profiles/r3/15).
-    const DecRoute rt = dec_route(sp, M, sw, dec_mlp_min_rows());
+    // att_maps: the weights are taken from the rows cross_apply reads, which the fused out_proj + cross kernel never writes - such a call
+    // routes as one with that kernel switched off (every other switch as the caller's)
+    DecSwitches swr = sw;
+    if (att_maps != nullptr) swr.out_cross = 0;
+    const DecRoute rt = dec_route(sp, M, swr, dec_mlp_min_rows());
     const Seq c{sp, M, s};
     const DecoderW& wm = mfma_table(w, wsp);
     Twin P[4], SK[NSKIP];
@@ -135,6 +142,10 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         else if (sp) { LADIFF_TRY(launch_gemm(proj(c, att_x, D, out, r1, D, D, ACT_NONE, cur.f), s)); DEC_CUT(); }
         else { LADIFF_TRY(gemm_ln(c, att_x, D, out, cur.f, L.norm1, nullptr, r1, true)); DEC_CUT(); }
         const NormW n1_late = sp ? L.norm1 : NormW{nullptr, nullptr};
+        if (att_maps != nullptr) {      // the layer's map [B][F][T] from the same rows, folded keys and counts (dec_cross.hip)
+            LADIFF_TRY(launch_decoder_cross_maps(P[1].f, counts, lengths, B, F, T, gu, att_maps + (size_t)l * B * F * T, s, row_off, n1_late.g,
+                                                 n1_late.b)); DEC_CUT();
+        }
         LADIFF_TRY(launch_decoder_cross_apply(P[1].f, L.cross_attn.out_b, L.norm2.g, L.norm2.b, counts, B, F, T, gu, P[2].f, P[2].s, s, row_off,
                                               n1_late.g, n1_late.b)); DEC_CUT();
         return 0;

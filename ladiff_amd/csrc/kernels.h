@@ -104,6 +104,10 @@ int launch_decoder_out_cross(const float* att_s, const float* x0, const float* w
 int launch_decoder_cross_apply(const float* x, const float* bo, const float* g2, const float* b2, const int32_t* counts, int B, int F,
                                int T, const float* gu_ws, float* y, float* ys, hipStream_t s, const int32_t* row_off = nullptr,
                                const float* g1 = nullptr, const float* b1 = nullptr);
+// the head-averaged cross-attention weights of the rows cross_apply reads (same x, g1 / b1, gu_ws): maps [B][F][T], frames >= lengths[b]
+// and tokens >= counts[b] zero
+int launch_decoder_cross_maps(const float* x, const int32_t* counts, const int32_t* lengths, int B, int F, int T, const float* gu_ws,
+                              float* maps, hipStream_t s, const int32_t* row_off, const float* g1, const float* b1);
 
 // feats2joints.hip
 int launch_feats2joints(const float* feats, const float* mean, const float* stdv, int B, int F, int C, int J, float* joints,

@@ -49,8 +49,10 @@ int dec_mlp_prepare();           // per-device kernel attributes (dynamic LDS): 
 int dec_qkv_attn_prepare();
 int dec_cross_prepare();
 int dec_mlp_min_rows();
+// att_maps (optional, [NL][B][F][T]): the head-averaged cross-attention weights of every layer as well (an analysis call, nine launches more)
 int vae_decode(const DecoderW& w, const DecoderW* w_split, const float* z, const int32_t* lengths, const int32_t* counts,
-               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s, const DecSwitches& sw);
+               const int32_t* row_off, int R, int B, int F, int T, int C, float* feats, float* ws, size_t ws_floats, hipStream_t s, const DecSwitches& sw,
+               float* att_maps = nullptr);
 
 // dec_mlp.hip: the decoder layer's feed-forward block (linear1, GELU, linear2, residual, LayerNorm[s]) as one kernel, f16x3 mode
 int launch_dec_mlp(const float* xs, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3,

@@ -379,10 +379,46 @@ class LADiffVae(_HipModule):
             cur.wait_stream(run)
         return out
 
-    def decode(self, z, lengths, plot_att_map=None, latentwise_gen=None):
-        """z [max_it,B,256], lengths list[int] -> feats [B, max(lengths), nfeats]; frames >= len are zero."""
-        if plot_att_map:
-            raise NotImplementedError("plot_att_map (matplotlib debug heat-maps, cross_attention.py:378-406) is not built")
+    # the decoder's blocks in execution order, as the reference names their heat-maps (cross_attention.py:130, :138, :148)
+    att_map_names = tuple([f"input_block_{i}" for i in range(4)] + ["middle_block"] + [f"output_block_{i}" for i in range(4)])
+
+    def _write_att_maps(self, directory, maps):
+        """<directory>/<name>.npy per block ([F,T] when B == 1, what the reference's torch.squeeze leaves; else [B,F,T]) and a viridis
+        heat-map <name>.png (<name>_b<k>.png per sample when B > 1), frames against latents: cross_attention.py:378-406 without its
+        seaborn / obspy / font settings.  Without matplotlib only the .npy files are written."""
+        import os
+        import warnings
+        directory = os.fspath(directory)
+        os.makedirs(directory, exist_ok=True)
+        host = maps.detach().cpu().numpy()
+        B = host.shape[1]
+        try:
+            from matplotlib.backends.backend_agg import FigureCanvasAgg      # the Agg canvas directly: no pyplot, no global backend switch
+            from matplotlib.figure import Figure
+        except ImportError:
+            Figure = None
+            warnings.warn("plot_att_map: matplotlib is not installed, only the .npy files are written", RuntimeWarning, stacklevel=3)
+        for name, m in zip(self.att_map_names, host):
+            np.save(os.path.join(directory, name + ".npy"), m[0] if B == 1 else m)
+            if Figure is None:
+                continue
+            for k in range(B):
+                fig = Figure(figsize=(4.5, 6.0))
+                FigureCanvasAgg(fig)
+                ax = fig.add_subplot(111)
+                im = ax.imshow(m[k], cmap="viridis", aspect="auto", interpolation="nearest", vmin=0.0, vmax=1.0)
+                ax.set_xlabel("latents")
+                ax.set_ylabel("frames")
+                fig.colorbar(im, ax=ax)
+                fig.savefig(os.path.join(directory, name + (".png" if B == 1 else f"_b{k}.png")), bbox_inches="tight")
+
+    def decode(self, z, lengths, plot_att_map=None, latentwise_gen=None, return_att_maps=False):
+        """z [max_it,B,256], lengths list[int] -> feats [B, max(lengths), nfeats]; frames >= len are zero.
+
+        return_att_maps=True -> (feats, maps): maps [9,B,F,max_it] float32 on the device, the head-averaged cross-attention weights of
+        the nine blocks (`att_map_names`, execution order), frames against latents; latents >= the sample's count and frames >= its
+        length are zero.  plot_att_map=<directory> writes them as .npy files and heat-maps (`_write_att_maps`) and returns feats.
+        Either makes the decode an analysis call (ladiff_vae_decode_att_maps): never replayed from a captured graph."""
         L = _lib.lib()
         dev = z.device
         T, B, Dm = z.shape
@@ -407,11 +443,27 @@ class LADiffVae(_HipModule):
         zz = z.detach().to(torch.float32).contiguous()
         rows = sum(lengths)
         ragged = self.length_aware and rows < B * F
-        if self.graph_rows and (rows if ragged else B * F) < self.graph_rows:
+        want_maps = bool(plot_att_map) or bool(return_att_maps)
+        if self.graph_rows and (rows if ragged else B * F) < self.graph_rows and not want_maps:
             return self._decode_graphed(zz, lengths, counts, counts_t, lens_t, rows if ragged else 0, wt, wsplit).to(z.dtype)
         feats = torch.empty(B, F, self.nfeats, dtype=torch.float32, device=dev)
         wsb = L.ladiff_decoder_workspace_bytes(B, F, T, self.nfeats)
         ws = _lib.workspace(wsb, dev)
+        if want_maps:
+            maps = torch.empty(len(self.att_map_names), B, F, T, dtype=torch.float32, device=dev)
+            off_t = None
+            if ragged:                                             # the ragged rows exactly when an ordinary decode takes them
+                off = [0] * (B + 1)
+                for i, l in enumerate(lengths):
+                    off[i + 1] = off[i] + l
+                off_t = _lib.device_ints(off, dev)
+            _lib.check(L.ladiff_vae_decode_att_maps(wt.array, wsplit, _lib.ptr(zz), lens_t.data_ptr(),
+                                                    None if counts_t is None else counts_t.data_ptr(),
+                                                    None if off_t is None else off_t.data_ptr(), rows if ragged else 0, B, F, T,
+                                                    self.nfeats, _lib.ptr(feats), _lib.ptr(maps), _lib.ptr(ws), wsb, _lib.stream_ptr()))
+            if plot_att_map:
+                self._write_att_maps(plot_att_map, maps)
+            return (feats.to(z.dtype), maps) if return_att_maps else feats.to(z.dtype)
         if ragged:
             # mixed lengths: only the valid frames are computed (ragged rows, ladiff_vae_decode_ragged); same frames out
             off = [0] * (B + 1)

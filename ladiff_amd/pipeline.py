@@ -732,20 +732,24 @@ class LADIFF(nn.Module):
 
     # ------------------------------------------------------------------ callers' surface
     def sample(self, text_emb, lengths, init_noise=None, step_noise=None, check=True, noise_seed=None, *, guidance_scale=None, seeds=None,
-               prompt_index=None, source_latents=None, strength=None, start_steps=None):
+               prompt_index=None, source_latents=None, strength=None, start_steps=None, return_att_maps=False):
         """text embeddings -> (z [max_it,B,256], feats [B,max(len),nfeats]): ladiff.py:266 + :283.  Returns checked frames: the
         decode is queued, then the host waits for the loop's status words (LadiffHipError if the loop was abandoned).
         check=False skips the wait (the host may then queue a call ahead) - the caller owes a `check()` before using the frames.
         guidance_scale / seeds / prompt_index: one value per prompt, see `_diffusion_reverse`.
-        source_latents with strength or start_steps: an edit of those latents instead of a sample from noise, see there."""
+        source_latents with strength or start_steps: an edit of those latents instead of a sample from noise, see there.
+        return_att_maps=True -> (z, feats, maps): the decoder's cross-attention weights [9,B,F,max_it] of that z (`LADiffVae.decode`)."""
         edit = {} if source_latents is None and strength is None and start_steps is None else \
             {"source_latents": source_latents, "strength": strength, "start_steps": start_steps}
         z = self._diffusion_reverse(text_emb, lengths, init_noise=init_noise, step_noise=step_noise, noise_seed=noise_seed,
                                     guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index, **edit)
-        feats = self.vae.decode(z, lengths)
+        if return_att_maps:
+            feats, maps = self.vae.decode(z, lengths, return_att_maps=True)
+        else:
+            feats = self.vae.decode(z, lengths)
         if check:
             self.check()
-        return z, feats
+        return (z, feats, maps) if return_att_maps else (z, feats)
 
     def forward(self, batch, latentwise_gen=None, plot_att_map=None):
         texts, lengths = batch["text"], batch["length"]
