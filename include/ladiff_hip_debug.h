@@ -55,7 +55,10 @@ LADIFF_API int ladiff_debug_set_xcd_local(int on);
  * decoder's self-attention as in_proj GEMM + attention kernel (two launches, q | k | v rows through memory) instead of the kernel
  * that computes its head's q | k | v itself (csrc/dec_qkv_attn.hip; default from 4,096 frame rows up); + 32: that kernel at every size.
  * + 64: the self-attention out_proj GEMM and the cross-attention row kernel as two launches (x + out_proj(att) through memory) instead
- * of the one kernel that keeps out_proj's weight in registers (csrc/dec_cross.hip; default from 4,096 frame rows up in f16x3 mode). */
+ * of the one kernel that keeps out_proj's weight in registers (csrc/dec_cross.hip; default from 4,096 frame rows up in f16x3 mode).
+ * + 128: where both that kernel and the fused feed-forward kernel would run (by default from 10,000 frame rows up), they run as
+ * two launches instead of the ONE kernel of csrc/dec_post.hip (out_proj .. norm3 on the feed-forward kernel's weight stream: another
+ * summation order, same products).  A call that asks for the attention maps never takes that kernel. */
 LADIFF_API int ladiff_debug_set_decoder_fusion(int on);
 /* Measurement switch (process-wide) of the fused feed-forward kernel's form: 0 (default) = chosen by the row count, 1 = 128-row
  * workgroups of eight waves x 16 rows, 2 = 64-row workgroups of four waves x 16 rows, 3 = 128-row workgroups of four waves x 32 rows.

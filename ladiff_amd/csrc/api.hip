@@ -304,7 +304,8 @@ int ladiff_debug_set_mlp_variant(int v) {
 }
 
 int ladiff_debug_set_decoder_fusion(int on) {
-    LADIFF_CHECK_ARG(on >= 0 && on <= 126 && (on & 3) != 3 && (on & 48) != 48);
+    LADIFF_CHECK_ARG(on >= 0 && on <= 254 && (on & 3) != 3 && (on & 48) != 48);
+    g_dec.post_off = (on & 128) ? 1 : 0;
     g_dec.out_cross = (on & 64) ? 0 : 1;
     g_dec.fused_mlp = on & 3;
     g_dec.small_rows_path = (on & 4) ? 0 : 1;
@@ -823,6 +824,7 @@ int ladiff_vae_decode_graphed(void* graph, const float* const* w, const float* c
         LADIFF_TRY(dec_mlp_prepare());            // kernel attributes are set outside the capture
         LADIFF_TRY(dec_qkv_attn_prepare());
         LADIFF_TRY(dec_cross_prepare());
+        LADIFF_TRY(dec_post_prepare());
         LADIFF_TRY(dg->cap.ensure());
         LADIFF_TRY(capture_graph(dg->cap.s, [&](hipStream_t cs) {
             // inside the capture: a zero-fill KERNEL, never a memset node (g_graph_epoch)

@@ -30,11 +30,13 @@ DecSwitchAtoms g_dec;                          // the measurement switches (mode
 //   f16x3 small (7)     in_proj gemm_kr | self-attention (split) | out_proj gemm_kr (+ residual) | cross_apply (norm1 as it loads) | linear1 gemm_kr |
 //                       linear2 gemm_kr (four K planes) | reduce_rows (sum + residual + norm3 [+ decoder.norm])
 //   f16x3 large-M (5)   dec_qkv_attn (in_proj inside) | out_cross (out_proj .. norm2) | linear1 gemm | linear2 gemm (+ residual) | reduce_rows
-//                       (norm3 [+ decoder.norm]);  from dec_mlp_min_rows() rows (3): dec_mlp instead of the last three
+//                       (norm3 [+ decoder.norm]);  from dec_mlp_min_rows() rows (3): dec_mlp instead of the last three; where out_cross
+//                       and dec_mlp both run (2): dec_post instead of the two (out_proj .. norm3 in one kernel), + 1 launch up front
+//                       (dec_post_gu: every layer's U transposed in place)
 //   layer 0: in_proj once on the F position rows (broadcast_pe + gemm / gemm_kr), never inside the attention kernel.  Output blocks (+ 1): the
 //   skip concat first (gemm; small: gemm_rowln).  Switches - small_rows_path 0: the large-M forms at any row count;  fused_attn 0: in_proj gemm +
 //   self-attention (split), 2: dec_qkv_attn below 4,096 rows too;  out_cross 0: out_proj gemm + cross_apply;  fused_mlp 0: never dec_mlp, 2: always;
-//   final_split 0: final_layer on the fp32 gemm as in fp32 mode, else pad_rows + gemm + scatter_feats
+//   final_split 0: final_layer on the fp32 gemm as in fp32 mode, else pad_rows + gemm + scatter_feats;  post_off 1: never dec_post
 // att_maps != nullptr ([NL][B][F][T], layers in execution order): out_cross off for this call, and cross_maps (+ 1 per layer) between the
 //   out_proj gemm and cross_apply.  A call without it makes the launches above.
 int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int32_t* lengths, const int32_t* counts,
@@ -85,6 +87,8 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         }
         LADIFF_TRY(launch_gemm_batch(g, NL, s)); DEC_CUT();
         LADIFF_TRY(launch_decoder_cross_prep(pb, NL, B, T, s)); DEC_CUT();
+        // the one-kernel layer tail reads U transposed: every layer's U rows re-laid in place, one launch (dec_post.hip)
+        if (rt.post) { LADIFF_TRY(launch_dec_post_gu(guws, a.gu_layer, NL, B, T, s)); DEC_CUT(); }
     }
 
     // a projection of the small route over `rows` rows (gemm_kr.hip; the route exists in f16x3 mode only)
@@ -171,6 +175,17 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         return 0;
     };
 
+    // the two steps above as ONE launch (dec_post.hip): x0 + out_proj(att), norm1's output and the feed-forward input are never written
+    auto post_attention = [&](Twin dst) -> int {
+        const LinearW out = out_proj(L.self_attn); const float* gu = guws + l * a.gu_layer;
+        const NormW* fin = l == NL - 1 ? &w.norm : nullptr;
+        const DecPostArgs pa{att, cur.f, out.w, out.b, L.norm1.g, L.norm1.b, gu, gu + (size_t)B * H * T * 2 * D, L.cross_attn.out_b, L.norm2.g,
+                             L.norm2.b, counts, row_off, L.lin1.w, L.lin1.b, L.lin2.w, L.lin2.b, L.norm3.g, L.norm3.b,
+                             fin ? fin->g : nullptr, fin ? fin->b : nullptr, dst.f, dst.s, B, F, T, M};
+        LADIFF_TRY(launch_dec_post(pa, s)); DEC_CUT();
+        return 0;
+    };
+
     // queries = zeros + query_pos_decoder.pe[:F]     ladiff_vae.py:299, :334
     if (ragged) { LADIFF_TRY(launch_broadcast_pe_ragged(w.query_pe, row_off, B, F, F, P[0].f, P[0].s, a.row_out, s)); DEC_CUT(); }
     else { LADIFF_TRY(launch_broadcast_pe(w.query_pe, B, F, P[0].f, P[0].s, s)); DEC_CUT(); }
@@ -178,9 +193,12 @@ int vae_decode(const DecoderW& w, const DecoderW* wsp, const float* z, const int
         L = mixed(w.layer[l], wm.layer[l]);
         if (l > NSKIP) DEC_STEP(skip_concat());
         DEC_STEP(self_attention());
-        DEC_STEP(out_proj_cross_attention());
         const Twin dst = l < NSKIP ? SK[l] : P[0];
-        DEC_STEP(feed_forward(dst));
+        if (rt.post) DEC_STEP(post_attention(dst));
+        else {
+            DEC_STEP(out_proj_cross_attention());
+            DEC_STEP(feed_forward(dst));
+        }
         cur = dst;
     }
     // final_layer + zero padded frames, written as [B, F, C]   ladiff_vae.py:356-360

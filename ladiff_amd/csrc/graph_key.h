@@ -12,7 +12,7 @@
 namespace ladiff {
 
 struct GraphKey {
-    static constexpr int CAPACITY = 36;                  // entries; the sampler's key has 30, 31 with x0_prev, up to 34 with z0 / starts / first_step, the decode graph's 21.  One too many aborts.
+    static constexpr int CAPACITY = 36;                  // entries; the sampler's key has 30, 31 with x0_prev, up to 34 with z0 / starts / first_step, the decode graph's 22.  One too many aborts.
     uint64_t v[CAPACITY] = {0};
     int n = 0;
 
@@ -138,12 +138,14 @@ struct DecSwitches {              // one reading of the decoder's measurement sw
     int out_cross;                // (+ 64 clears it): out_proj + cross-attention in one kernel, else the GEMM + the row kernel as two launches (the path before)
     int fused_attn;               // (+ 16 clears it, + 32 = always): in_proj inside the attention kernel, else GEMM + attention kernel as two launches (the path before)
     int mlp_variant;              // ladiff_debug_set_mlp_variant: workgroup form of the fused feed-forward kernel
+    int post_off;                 // (+ 128 sets it): 0 = out_proj .. norm2 + the feed-forward in ONE kernel where both fused forms run, 1 = as two launches (the path before)
 };
 // Which launches a decode makes (decoder.hip), decided once per call; vae_decode branches on nothing else.  small: the GEMMs on the small-M
 // kernels; fused_attn: in_proj inside the attention kernel; out_cross: out_proj .. norm2 in one kernel (never on the small route); fused_mlp: the
-// feed-forward block in one kernel; final_split: final_layer on padded f16x3 tiles.  All false in fp32 mode (truth table: tests/graph_key_check.cpp).
+// feed-forward block in one kernel; final_split: final_layer on padded f16x3 tiles; post: out_cross and fused_mlp as ONE kernel (dec_post.hip).
+// All false in fp32 mode (truth tables: tests/graph_key_check.cpp, tests/dec_post_route_check.cpp).
 constexpr int DEC_SMALL_ROWS = 4096;
-struct DecRoute { bool small, fused_attn, out_cross, fused_mlp, final_split; };
+struct DecRoute { bool small, fused_attn, out_cross, fused_mlp, final_split, post; };
 inline DecRoute dec_route(bool split_mode, int rows, const DecSwitches& sw, int mlp_min_rows) {
     DecRoute r;
     r.small = split_mode && rows < DEC_SMALL_ROWS && sw.small_rows_path;
@@ -151,6 +153,7 @@ inline DecRoute dec_route(bool split_mode, int rows, const DecSwitches& sw, int 
     r.out_cross = split_mode && !r.small && sw.out_cross;
     r.fused_mlp = split_mode && sw.fused_mlp && (rows >= mlp_min_rows || sw.fused_mlp == 2);
     r.final_split = split_mode && rows >= DEC_SMALL_ROWS && sw.final_split;
+    r.post = r.out_cross && r.fused_mlp && !r.small && !sw.post_off;
     return r;
 }
 // Key of a decode graph (ladiff_vae_decode_graphed): EVERY field of the call's switch snapshot is part of it.
@@ -177,6 +180,7 @@ inline GraphKey decode_key(const float* const* w, const float* const* w_split, i
     k.add(sw.mlp_variant);
     k.add(sw.fused_attn);
     k.add(sw.out_cross);
+    k.add(sw.post_off);
     k.add(weights_hash(w, w_split, n_params));
     k.add(weights_generation);
     return k;

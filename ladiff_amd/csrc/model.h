@@ -41,8 +41,8 @@ int diffusion_reverse(Sampler* sp, const DenoiserW& w, const DenoiserW* w_split,
 // decoder.hip.  Its measurement switches (ladiff_debug_set_decoder_fusion / _mlp_variant), an object like the loop's (systolic_plan.h, g_loop): a decode
 // reads them ONCE - the snapshot (DecSwitches, graph_key.h) routes the whole call and is in its graph's key
 struct DecSwitchAtoms {
-    std::atomic<int> fused_mlp{1}, small_rows_path{1}, final_split{1}, out_cross{1}, fused_attn{1}, mlp_variant{0};
-    DecSwitches snapshot() const { return {fused_mlp, small_rows_path, final_split, out_cross, fused_attn, mlp_variant}; }
+    std::atomic<int> fused_mlp{1}, small_rows_path{1}, final_split{1}, out_cross{1}, fused_attn{1}, mlp_variant{0}, post_off{0};
+    DecSwitches snapshot() const { return {fused_mlp, small_rows_path, final_split, out_cross, fused_attn, mlp_variant, post_off}; }
 };
 extern DecSwitchAtoms g_dec;
 int dec_mlp_prepare();           // per-device kernel attributes (dynamic LDS): outside any stream capture, under a mutex
@@ -57,6 +57,23 @@ int vae_decode(const DecoderW& w, const DecoderW* w_split, const float* z, const
 // dec_mlp.hip: the decoder layer's feed-forward block (linear1, GELU, linear2, residual, LayerNorm[s]) as one kernel, f16x3 mode
 int launch_dec_mlp(const float* xs, const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3,
                    const float* be3, const float* g4, const float* be4, float* y, float* ys, int M, hipStream_t s, int variant);      // DecSwitches::mlp_variant
+
+// dec_post.hip: out_proj + norm1 + cross-attention + norm2 + the feed-forward block above as one kernel, f16x3 mode (DecRoute::post)
+struct DecPostArgs {
+    const float* att;          // [M,256] S-format: the self-attention output (heads concatenated)
+    const float* x0;           // [M,256] fp32: the layer input (residual)
+    const float* wo;           // self_attn.out_proj.weight [256,256] S-format
+    const float *bo, *g1, *be1;                    // out_proj bias, norm1
+    const float *gu, *cc;                          // the layer's G | U^T (launch_dec_post_gu's layout) and score offsets
+    const float *bo_c, *g2, *be2;                  // cross-attention out_proj bias, norm2
+    const int32_t *counts, *row_off;
+    const float *w1, *b1, *w2, *b2, *g3, *be3, *g4, *be4;      // as launch_dec_mlp
+    float *y, *ys;             // fp32 / S-format results (either may be NULL)
+    int B, F, T, M;
+};
+int dec_post_prepare();          // per-device kernel attribute, as dec_mlp_prepare
+int launch_dec_post_gu(float* guws, size_t gu_layer, int n, int B, int T, hipStream_t s);
+int launch_dec_post(const DecPostArgs& a, hipStream_t s);
 
 int vae_encode(const EncoderW& w, const EncoderW* w_split, const float* features, const int32_t* lengths,
                const int32_t* counts, const float* eps, int B, int F, int T, int C, float* mu, float* sd, float* latent, float* ws,
