@@ -270,6 +270,17 @@ LADIFF_API int ladiff_cfg_scheduler_step_from(const float* eps, float* latents /
                               float* x0_prev /*[B,T,256] in/out, or NULL*/, const float* coef, const int32_t* d_step,
                               const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale, int cfg, int B, int T,
                               const int32_t* starts /*[B] device or NULL*/, int first_step, ladiff_stream_t stream);
+/* The same step with its record: the unit entry of the rule behind ladiff_diffusion_reverse_record.  traj_x / traj_x0 [n,B,T,256] fp32
+ * device, 16-byte aligned (else LADIFF_ERR_SHAPE), the layout of step_noise; either or both may be NULL.  Only row s = *d_step is written:
+ *   traj_x[s]   the latents after the step, the bits stored to `latents` (scheduler.step(...).prev_sample, ladiff.py:706-734);
+ *   traj_x0[s]  the step's data prediction (x - sqrt(1-a_s) eps) / sqrt(a_s), eps the guided prediction (pred_original_sample);
+ *   a frozen row (s < s_b): traj_x[s] = its latents as they stand, traj_x0[s] = 0.
+ * Every other row of both buffers keeps its contents.  With both NULL this is ladiff_cfg_scheduler_step_from. */
+LADIFF_API int ladiff_cfg_scheduler_step_record(const float* eps, float* latents /*[B,T,256] in/out*/,
+                              float* x0_prev /*[B,T,256] in/out, or NULL*/, const float* coef, const int32_t* d_step,
+                              const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale, int cfg, int B, int T,
+                              const int32_t* starts /*[B] device or NULL*/, int first_step, float* traj_x /*[n,B,T,256] or NULL*/,
+                              float* traj_x0 /*[n,B,T,256] or NULL*/, ladiff_stream_t stream);
 LADIFF_API int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream);
 
 /* latents[B,T,256] = noise * valid * sigma  (ladiff.py:380-390, :407) */
@@ -448,6 +459,31 @@ LADIFF_API int ladiff_diffusion_reverse_from(void* sampler, const float* const* 
                              const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
                              int draw_init_noise, float* x0_prev /*[B,T,256] device, or NULL*/, const float* z0 /*[T,B,256] device, or NULL*/,
                              const int32_t* starts /*[B] device or NULL*/, int first_step, ladiff_stream_t stream);
+/* The same loop with its DENOISING TRAJECTORY recorded (the reference's _diffusion_reverse_tsne, ladiff.py:706-734: latents appended after
+ * every scheduler.step).  traj_x / traj_x0 [n_steps,B,T,256] fp32 device, the caller's, 16-byte aligned (else LADIFF_ERR_SHAPE), the layout
+ * of step_noise; either or both may be NULL, with both NULL this is ladiff_diffusion_reverse_from exactly (which forwards here).  For every
+ * position s the call runs (first_step <= s < n_steps; rows s < first_step are not touched):
+ *   traj_x[s]   the latents after position s - scheduler.step(...).prev_sample, the bits the step stores to the latents;
+ *   traj_x0[s]  the step's data prediction (x_s - sqrt(1-a_s) eps_s) / sqrt(a_s), eps the guided prediction;
+ *   rows t >= final_counts[b] are exact zeros in both (final_counts NULL: no such rows);
+ *   while prompt b is frozen (z0 set, s < starts[b]) traj_x[s] holds its latents as they stand (the noised source), traj_x0[s] zeros.
+ * Row indices are positions of the full schedule, whatever windows the loop runs in.  Recording changes no arithmetic: z keeps the bits of
+ * the same call without it, in every loop form.  The pointers are part of a sampler's key (on or off, which kinds, where); new values in
+ * the same buffers replay what is there.  The persistent pipeline records loops from noise; a recording call with z0 runs as step graphs
+ * (ladiff_sampler_last_loop says so).  n_text > 1 with either buffer is LADIFF_ERR_UNSUPPORTED.  No workspace size changes. */
+LADIFF_API int ladiff_diffusion_reverse_record(void* sampler, const float* const* w, const float* const* w_split /*or NULL*/,
+                             uint64_t weights_generation, const float* text_emb /*[2B or B,n_text,768]*/,
+                             const float* init_noise /*[B,T,256], or NULL with draw_init_noise*/, const int32_t* counts /*[B] or NULL*/,
+                             const int32_t* final_counts /*[B] or NULL*/,
+                             const int32_t* h_counts /*HOST copy of counts, or NULL*/,
+                             const float* sinusoid /*[n,768]*/, const float* coef /*[n,8]*/,
+                             const float* step_noise /*[n,B,T,256] or NULL*/, float guidance_scale,
+                             float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z /*[T,B,256]*/,
+                             void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales /*[B] device or NULL*/,
+                             const uint64_t* seeds /*[B] device or NULL*/, const uint32_t* prompt_index /*[B] device or NULL*/,
+                             int draw_init_noise, float* x0_prev /*[B,T,256] device, or NULL*/, const float* z0 /*[T,B,256] device, or NULL*/,
+                             const int32_t* starts /*[B] device or NULL*/, int first_step, float* traj_x /*[n,B,T,256] device, or NULL*/,
+                             float* traj_x0 /*[n,B,T,256] device, or NULL*/, ladiff_stream_t stream);
 /* The per-prompt generator's values as a tensor: out[i][b][t][:] for schedule positions first_step + i of the prompt with key seeds[b]
  * and index prompt_index[b]; first_step = -1 starts at the initial noise.  first_step < -1 is LADIFF_ERR_ARG. */
 LADIFF_API int ladiff_noise_fill_prompts(const uint64_t* seeds /*[B] device*/, const uint32_t* prompt_index /*[B] device or NULL*/,

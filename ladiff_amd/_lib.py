@@ -86,6 +86,8 @@ _SIGNATURES = {
                                                     c_int, c_void_p]),
     "ladiff_cfg_scheduler_step_from": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
                                                c_int, c_void_p, c_int, c_void_p]),
+    "ladiff_cfg_scheduler_step_record": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int,
+                                                 c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ladiff_advance_step": (c_int, [c_void_p, c_void_p]),
     "ladiff_init_latents": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
     "ladiff_init_latents_from": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
@@ -125,6 +127,10 @@ _SIGNATURES = {
                                               c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_int, c_int,
                                               c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                               c_void_p, c_void_p, c_int, c_void_p]),
+    "ladiff_diffusion_reverse_record": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_int, c_int,
+                                                c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                                c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ladiff_noise_fill_prompts": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ladiff_encoder_num_params": (c_int, []),
     "ladiff_encoder_param_name": (c_char_p, [c_int]),

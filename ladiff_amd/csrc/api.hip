@@ -202,8 +202,9 @@ int ladiff_linear_cross_attention(const float* const* w, int layer, const float*
 
 // ------------------------------------------------------------------ guidance + scheduler
 // the step end of the three entries below: no generator and no per-prompt scales
-static StepEnd step_end(const float* coef, const float* step_noise, float guidance_scale, int cfg, float* x0_prev, bool edit, const int32_t* starts, int first_step) {
-    return StepEnd{coef, step_noise, NoiseGen{0u, 0u, 0u, 0}, guidance_scale, nullptr, cfg, x0_prev, edit, starts, first_step};
+static StepEnd step_end(const float* coef, const float* step_noise, float guidance_scale, int cfg, float* x0_prev, bool edit, const int32_t* starts, int first_step,
+                        float* traj_x = nullptr, float* traj_x0 = nullptr) {
+    return StepEnd{coef, step_noise, NoiseGen{0u, 0u, 0u, 0}, guidance_scale, nullptr, cfg, x0_prev, edit, starts, first_step, traj_x, traj_x0, nullptr};
 }
 int ladiff_cfg_scheduler_step(const float* eps, float* latents, const float* coef, const int32_t* d_step,
                               const float* step_noise, float guidance_scale, int cfg, int B, int T,
@@ -223,6 +224,16 @@ int ladiff_cfg_scheduler_step_from(const float* eps, float* latents, float* x0_p
     LADIFF_CHECK_ARG(eps && latents && coef && d_step && B > 0 && T > 0 && first_step >= 0);
     if ((reinterpret_cast<uintptr_t>(x0_prev) & 15) || (reinterpret_cast<uintptr_t>(starts) & 3)) return LADIFF_ERR_SHAPE;
     return launch_cfg_step(eps, latents, d_step, step_end(coef, step_noise, guidance_scale, cfg, x0_prev, true, starts, first_step), B, T, S(stream));
+}
+int ladiff_cfg_scheduler_step_record(const float* eps, float* latents, float* x0_prev, const float* coef, const int32_t* d_step,
+                                     const float* step_noise, float guidance_scale, int cfg, int B, int T, const int32_t* starts, int first_step,
+                                     float* traj_x, float* traj_x0, ladiff_stream_t stream) {
+    LADIFF_CHECK_ARG(eps && latents && coef && d_step && B > 0 && T > 0 && first_step >= 0);
+    if ((reinterpret_cast<uintptr_t>(x0_prev) & 15) || (reinterpret_cast<uintptr_t>(starts) & 3) || (reinterpret_cast<uintptr_t>(traj_x) & 15) ||
+        (reinterpret_cast<uintptr_t>(traj_x0) & 15))
+        return LADIFF_ERR_SHAPE;
+    return launch_cfg_step(eps, latents, d_step, step_end(coef, step_noise, guidance_scale, cfg, x0_prev, true, starts, first_step, traj_x, traj_x0),
+                           B, T, S(stream));
 }
 int ladiff_advance_step(int32_t* d_step, ladiff_stream_t stream) {
     LADIFF_CHECK_ARG(d_step);
@@ -530,6 +541,19 @@ int ladiff_diffusion_reverse_from(void* sampler, const float* const* w, const fl
                                   void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales, const uint64_t* seeds,
                                   const uint32_t* prompt_index, int draw_init_noise, float* x0_prev, const float* z0, const int32_t* starts,
                                   int first_step, ladiff_stream_t stream) {
+    return ladiff_diffusion_reverse_record(sampler, w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid,
+                                           coef, step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
+                                           reuse_time_tables, guidance_scales, seeds, prompt_index, draw_init_noise, x0_prev, z0, starts, first_step,
+                                           nullptr, nullptr, stream);
+}
+
+int ladiff_diffusion_reverse_record(void* sampler, const float* const* w, const float* const* w_split, uint64_t weights_generation,
+                                    const float* text_emb, const float* init_noise, const int32_t* counts, const int32_t* final_counts,
+                                    const int32_t* h_counts, const float* sinusoid, const float* coef, const float* step_noise,
+                                    float guidance_scale, float init_noise_sigma, int cfg, int B, int T, int n_text, int n_steps, float* z,
+                                    void* ws, size_t ws_bytes, int reuse_time_tables, const float* guidance_scales, const uint64_t* seeds,
+                                    const uint32_t* prompt_index, int draw_init_noise, float* x0_prev, const float* z0, const int32_t* starts,
+                                    int first_step, float* traj_x, float* traj_x0, ladiff_stream_t stream) {
     DenoiserW W, WS;
     // a loop from a source motion: `starts` means nothing without z0, and the first position is one of the schedule's
     LADIFF_CHECK_ARG(starts == nullptr || z0 != nullptr);
@@ -544,14 +568,16 @@ int ladiff_diffusion_reverse_from(void* sampler, const float* const* w, const fl
     if (T < 1 || T > LADIFF_MAX_LATENTS || n_text < 1) return LADIFF_ERR_SHAPE;
     if ((reinterpret_cast<uintptr_t>(guidance_scales) & 3) || (reinterpret_cast<uintptr_t>(seeds) & 7) ||
         (reinterpret_cast<uintptr_t>(prompt_index) & 3) || (reinterpret_cast<uintptr_t>(x0_prev) & 15) ||
-        (reinterpret_cast<uintptr_t>(z0) & 15) || (reinterpret_cast<uintptr_t>(starts) & 3))
+        (reinterpret_cast<uintptr_t>(z0) & 15) || (reinterpret_cast<uintptr_t>(starts) & 3) || (reinterpret_cast<uintptr_t>(traj_x) & 15) ||
+        (reinterpret_cast<uintptr_t>(traj_x0) & 15))
         return LADIFF_ERR_SHAPE;
     if (z0 != nullptr && n_text != 1) return LADIFF_ERR_UNSUPPORTED;      // the text-sequence form has no loop from a source motion
+    if ((traj_x != nullptr || traj_x0 != nullptr) && n_text != 1) return LADIFF_ERR_UNSUPPORTED;      // nor a recorded trajectory
     return diffusion_reverse(reinterpret_cast<Sampler*>(sampler), W, w_split ? &WS : nullptr,
                              ReverseArgs{w, w_split, weights_generation, text_emb, init_noise, counts, final_counts, h_counts, sinusoid, coef,
                                          step_noise, guidance_scale, init_noise_sigma, cfg, B, T, n_text, n_steps, z, ws, ws_bytes,
                                          reuse_time_tables, stream, guidance_scales, seeds, prompt_index, draw_init_noise ? 1 : 0, x0_prev, z0,
-                                         z0 != nullptr ? starts : nullptr, z0 != nullptr ? first_step : 0});
+                                         z0 != nullptr ? starts : nullptr, z0 != nullptr ? first_step : 0, traj_x, traj_x0});
 }
 
 // ------------------------------------------------------------------ LA-VAE encoder

@@ -12,7 +12,7 @@
 namespace ladiff {
 
 struct GraphKey {
-    static constexpr int CAPACITY = 36;                  // entries; the sampler's key has 30, 31 with x0_prev, up to 34 with z0 / starts / first_step, the decode graph's 22.  One too many aborts.
+    static constexpr int CAPACITY = 40;                  // entries; the sampler's key has 30, 31 with x0_prev, up to 34 with z0 / starts / first_step, up to 37 with traj_x / traj_x0, the decode graph's 22.  One too many aborts.
     uint64_t v[CAPACITY] = {0};
     int n = 0;
 
@@ -76,6 +76,10 @@ struct ReverseArgs {
     const float* z0 = nullptr;
     const int32_t* starts = nullptr;
     int first_step = 0;
+    // ladiff_diffusion_reverse_record: the caller's [n_steps,B,T,256] buffers for the latents after each position / each position's data
+    // prediction, either or both null (nothing is recorded)
+    float* traj_x = nullptr;
+    float* traj_x0 = nullptr;
 };
 
 // Key of a sampler's graphs (prologue graph + step graph, or prologue graph + the pipeline's stage table).  n_params: pointers per weight
@@ -93,6 +97,9 @@ struct ReverseArgs {
 // first_step is baked in where a captured node holds it: the launch-per-stage form (its prologue sets the step counter) and a call without
 // `starts` (the prologue kernel noises every prompt to first_step).  A pipeline call with `starts` passes it as a launch argument only: not
 // keyed, new starts or a new first_step replay what is there.
+// traj_x / traj_x0 (ladiff_diffusion_reverse_record): the prologue graph (its padding rows) and the step graphs' tail nodes hold the pointers,
+// and a recording pipeline call runs other instantiations on another plan policy: keyed by pointer under a marker entry that only a recording
+// call has - on or off, which kinds and where are all part of the key, so a plan never replays a graph of the other kind.
 inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, int plan_mr, int plan_nb, const unsigned noise[4]) {
     GraphKey k;
     k.add(a.ws);
@@ -127,6 +134,11 @@ inline GraphKey sampler_key(const ReverseArgs& a, int n_params, bool pipeline, i
         k.add(a.z0);
         k.add(a.starts);
         k.add(!pipeline || a.starts == nullptr ? a.first_step : -1);
+    }
+    if (a.traj_x != nullptr || a.traj_x0 != nullptr) {
+        k.add((uint64_t)0x7472616a);                             // "traj": after it the two pointers, never a position an edit's entries take
+        k.add(a.traj_x);
+        k.add(a.traj_x0);
     }
     return k;
 }

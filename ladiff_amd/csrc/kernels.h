@@ -59,7 +59,13 @@ struct StepEnd {
     int cfg;                      // classifier-free guidance: the network ran on both branches
     float* x0_prev;               // [B,T,256] previous data prediction (multistep form), or null (one-step rule)
     bool edit; const int32_t* starts; int first_step;   // a loop from a source motion: prompt b enters the schedule at starts[b] ([B], device; null: at first_step), step_gate in step_rule.h
+    // the denoising trajectory ([n,B,T,256] each, or null): row `step` takes the latents after the step / the step's data prediction; rows
+    // t >= traj_counts[b] are left alone (the loop's prologue zeroed them, launch_traj_zero_pad); traj_counts null: every row is written.  DESIGN 8k
+    float *traj_x, *traj_x0; const int32_t* traj_counts;
+    bool record() const { return traj_x != nullptr || traj_x0 != nullptr; }
 };
+// rows t >= counts[b] of positions [first, n) of a trajectory buffer = 0 (counts null: nothing to do).  A kernel, as launch_zero_fill is
+int launch_traj_zero_pad(float* traj, const int32_t* counts, int first, int n, int B, int T, hipStream_t s);
 int launch_cfg_step(const float* eps, float* lat, const int32_t* d_step, const StepEnd& e, int B, int T, hipStream_t s);
 int launch_advance(int32_t* d_step, hipStream_t s);
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, int32_t* d_step, const float* pe, const StepEnd& e,

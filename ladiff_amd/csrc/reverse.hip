@@ -48,6 +48,10 @@ int prologue(const Call& c, hipStream_t st) {
     // [0] step index, [1] tail-kernel ticket, [2] window base.  A KERNEL, not hipMemsetAsync: this runs inside the captured prologue
     // graph, and a memset NODE is what an older exec replayed wrongly (see g_graph_epoch)
     if (!c.edit()) LADIFF_TRY(launch_zero_fill(reinterpret_cast<float*>(r.d_step), 4, st));
+    // a recorded trajectory: the rows past each prompt's latent count, of every position this call runs, are zeroed here (a kernel too) -
+    // no tail stores to them, and the pipeline's 16-row blocks do not even carry them
+    LADIFF_TRY(launch_traj_zero_pad(c.end.traj_x, c.end.traj_counts, c.first(), a.n_steps, a.B, a.T, st));
+    LADIFF_TRY(launch_traj_zero_pad(c.end.traj_x0, c.end.traj_counts, c.first(), a.n_steps, a.B, a.T, st));
     // One step = the nine denoiser layers + ONE tail launch (final LayerNorm of the guidance branches, guidance,
     // scheduler step, next step's network input, step counter).  The network input / last-layer output buffer of the
     // forward workspace is primed here.
@@ -174,14 +178,17 @@ int diffusion_reverse(Sampler* sp, const DenoiserW& W, const DenoiserW* WSp, con
     // enter the key are then constants, the arrays are keyed by pointer
     if (a.seeds != nullptr && a.step_noise == nullptr) gen = prompt_gen(a);
     Call c{W, WSp, a, carve_reverse(a.ws, a.B, a.T, a.n_steps, a.n_text), reinterpret_cast<hipStream_t>(a.stream), dup, dup * a.B,
-           StepEnd{a.coef, a.step_noise, gen, a.guidance_scale, a.guidance_scales, a.cfg, a.x0_prev, a.z0 != nullptr, a.starts, a.first_step},
+           StepEnd{a.coef, a.step_noise, gen, a.guidance_scale, a.guidance_scales, a.cfg, a.x0_prev, a.z0 != nullptr, a.starts, a.first_step,
+                   a.traj_x, a.traj_x0, a.final_counts},
            nullptr, nullptr, false, {}, 2, 0};
     if (a.ws_bytes < c.r.total_bytes) return LADIFF_ERR_WORKSPACE;
     den_loop_io(c.r.fwd, c.B2 * a.T, &c.xio, &c.xios);
     if (WSp == nullptr) c.xios = nullptr;
     // without guidance the pipeline runs one-branch 16-row blocks, which need the latent counts on the host (or no masking at all)
+    // a call that records its trajectory AND starts from a source motion does not qualify either: the pipeline has no instantiation that
+    // does both, it runs as step graphs
     c.pipeline = sp != nullptr && sp->loop == 1 && a.n_text == 1 && sys_supported(a.B, a.T, a.cfg, WSp != nullptr) &&
-                 (a.cfg || a.counts == nullptr || a.h_counts != nullptr);
+                 (a.cfg || a.counts == nullptr || a.h_counts != nullptr) && !(c.end.record() && c.edit());
     // Block geometry of the pipeline for THIS call's lengths.  16-row blocks carry only the valid latent rows of each prompt
     // (length-aware packing; needs the counts on the host), 32-row blocks the padded T rows.  A step costs the larger of (blocks x
     // the busiest stage's time per block) and one block's trip through the 59 stages: choose_plan() picks the cheaper plan.

@@ -508,6 +508,24 @@ int launch_zero_fill(float* x, size_t n, hipStream_t s) {
     return 0;
 }
 
+// rows t >= counts[b] of positions [first, n) of a trajectory buffer [n,B,T,256] = 0: the rows no tail writes (StepEnd::traj_counts).
+// One wave per (position, b, t) row.
+__global__ __launch_bounds__(256) void traj_zero_pad_kernel(float* __restrict__ traj, const int32_t* __restrict__ counts, int first,
+                                                            size_t rows, int B, int T) {
+    const size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);          // row of positions first ..
+    if (r >= rows) return;
+    const int bt = (int)(r % ((size_t)B * T));
+    if (bt % T < counts[bt / T]) return;
+    st4(traj + ((size_t)first * B * T + r) * D + (threadIdx.x & 63) * 4, f32x4{0.f, 0.f, 0.f, 0.f});
+}
+int launch_traj_zero_pad(float* traj, const int32_t* counts, int first, int n, int B, int T, hipStream_t s) {
+    if (traj == nullptr || counts == nullptr || n <= first) return 0;
+    const size_t rows = (size_t)(n - first) * B * T;
+    hipLaunchKernelGGL(traj_zero_pad_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, traj, counts, first, rows, B, T);
+    LADIFF_LAUNCH_CHECK();
+    return 0;
+}
+
 // dst [Np][256] = src [C][256] followed by zero rows, dstb [Np] = srcb [C] followed by zeros: the decoder's final_layer brought to whole
 // 128-column GEMM tiles INSIDE the library (an S-format row is 1 KiB like an fp32 one, and zero rows are zero in both formats), so that a
 // caller's table of C rows is never read past its end
@@ -563,12 +581,15 @@ int launch_sinusoid(const int64_t* t, int n, float* out, hipStream_t s) {
 // k_m != 0 (step-uniform, like the noise branch) and this step's x0 is left in it; null = the one-step rule, column 6 is not read.
 // ED (a loop from a source motion, step_gate in step_rule.h): prompt b enters at starts[b], or at first_step without the array.  A template
 // flag: the kernel without it is exactly the code it was.
-template <bool ED>
+// RC (the denoising trajectory, StepEnd::traj_x / traj_x0): row `step` of either buffer takes the bits stored to lat / this step's x0; a
+// frozen row (ED) records its latents as they stand and a zero x0; rows past trc[b] are the prologue's.  A template flag for the same reason.
+template <bool ED, bool RC>
 __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__ eps, float* __restrict__ lat,
                                                        const float* __restrict__ coef, const int32_t* __restrict__ d_step,
                                                        const float* __restrict__ noise, float g, const float* __restrict__ gs,
                                                        int cfg, int T, size_t n4, const NoiseGen gen, float* __restrict__ x0p,
-                                                       const int32_t* __restrict__ starts, int first_step) {
+                                                       const int32_t* __restrict__ starts, int first_step, float* __restrict__ trx,
+                                                       float* __restrict__ trx0, const int32_t* __restrict__ trc) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
     const int step = *d_step;
@@ -576,7 +597,15 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     if (gs != nullptr) g = gs[row / T];                                  // the prompt's own scale (launch-uniform branch)
     StepCoef c = step_coef(coef, step, x0p != nullptr);
     if constexpr (ED) {
-        if (!step_gate(c, step, starts != nullptr ? starts[row / T] : first_step)) return;      // frozen: nothing of the row is touched
+        if (!step_gate(c, step, starts != nullptr ? starts[row / T] : first_step)) {            // frozen: nothing of the row is touched
+            if constexpr (RC) {
+                if (trc == nullptr || row % T < trc[row / T]) {
+                    if (trx != nullptr) st4(trx + ((size_t)step * n4 + i) * 4, ld4(lat + i * 4));
+                    if (trx0 != nullptr) st4(trx0 + ((size_t)step * n4 + i) * 4, f32x4{0.f, 0.f, 0.f, 0.f});
+                }
+            }
+            return;
+        }
     }
     f32x4 e = ld4(eps + i * 4);
     if (cfg) e = guide4(e, ld4(eps + (n4 + i) * 4), g);
@@ -585,11 +614,19 @@ __global__ __launch_bounds__(256) void cfg_step_kernel(const float* __restrict__
     const f32x4 m0 = step_rule4(x, e, z, x0p + i * 4, c);
     if (x0p != nullptr) st4(x0p + i * 4, m0);
     st4(lat + i * 4, x);
+    if constexpr (RC) {
+        if (trc == nullptr || row % T < trc[row / T]) {
+            if (trx != nullptr) st4(trx + ((size_t)step * n4 + i) * 4, x);
+            if (trx0 != nullptr) st4(trx0 + ((size_t)step * n4 + i) * 4, m0);
+        }
+    }
 }
 int launch_cfg_step(const float* eps, float* lat, const int32_t* d_step, const StepEnd& e, int B, int T, hipStream_t s) {
     const size_t n4 = (size_t)B * T * D / 4;
-    hipLaunchKernelGGL(e.edit ? cfg_step_kernel<true> : cfg_step_kernel<false>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat,
-                       e.coef, d_step, e.noise, e.g, e.gs, e.cfg, T, n4, e.gen, e.x0_prev, e.starts, e.first_step);
+    const auto fn = e.record() ? (e.edit ? cfg_step_kernel<true, true> : cfg_step_kernel<false, true>)
+                               : (e.edit ? cfg_step_kernel<true, false> : cfg_step_kernel<false, false>);
+    hipLaunchKernelGGL(fn, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, eps, lat, e.coef, d_step, e.noise, e.g, e.gs, e.cfg, T, n4,
+                       e.gen, e.x0_prev, e.starts, e.first_step, e.traj_x, e.traj_x0, e.traj_counts);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }
@@ -601,13 +638,15 @@ int launch_cfg_step(const float* eps, float* lat, const int32_t* d_step, const S
 // over the last layer's output (fp32 + optional S-format twin).  The last workgroup to finish bumps the step counter
 // (every workgroup has read it before taking its ticket), so the whole tail of a step is one launch instead of five.
 // ED: as for cfg_step_kernel; a frozen row still gets the next network input latent + pe (the network runs on every row of the launch).
-template <bool ED>
+// RC: as for cfg_step_kernel; the row index is d_step[0], so the captured step graph replays unchanged for every step.
+template <bool ED, bool RC>
 __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, float* __restrict__ xs, const float* __restrict__ ng,
                                                         const float* __restrict__ nb, float* __restrict__ lat,
                                                         const float* __restrict__ coef, int32_t* __restrict__ d_step,
                                                         const float* __restrict__ noise, const float* __restrict__ pe, float g,
                                                         const float* __restrict__ gs, int cfg, int B, int T, const NoiseGen gen,
-                                                        float* __restrict__ x0p, const int32_t* __restrict__ starts, int first_step) {
+                                                        float* __restrict__ x0p, const int32_t* __restrict__ starts, int first_step,
+                                                        float* __restrict__ trx, float* __restrict__ trx0, const int32_t* __restrict__ trc) {
     const int step = d_step[0];
     const int row = blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);      // row = b * T + t of the B prompts
     const int c = (threadIdx.x & 63) * 4;
@@ -655,6 +694,13 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
 #pragma unroll
         for (int i = 0; i < 4; ++i) xn[i] = l[i] + p[i];
         if (live) st4(lat + (size_t)row * D + c, l);
+        if constexpr (RC) {                  // l: the bits of lat, stored above or kept; a frozen row's x0 is zero
+            if (trc == nullptr || row % T < trc[row / T]) {
+                const size_t at = ((size_t)step * M + row) * D + c;
+                if (trx != nullptr) st4(trx + at, l);
+                if (trx0 != nullptr) st4(trx0 + at, live ? m0 : f32x4{0.f, 0.f, 0.f, 0.f});
+            }
+        }
         st4(x + (size_t)row * D + c, xn);
         if (cfg) st4(x + (size_t)(M + row) * D + c, xn);
         if (xs != nullptr) {
@@ -671,8 +717,10 @@ __global__ __launch_bounds__(256) void step_tail_kernel(float* __restrict__ x, f
 int launch_step_tail(float* x, float* xs, const float* ng, const float* nb, float* lat, int32_t* d_step, const float* pe, const StepEnd& e,
                      int B, int T, hipStream_t s) {
     const int M = B * T;
-    hipLaunchKernelGGL(e.edit ? step_tail_kernel<true> : step_tail_kernel<false>, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s,
-                       x, xs, ng, nb, lat, e.coef, d_step, e.noise, pe, e.g, e.gs, e.cfg, B, T, e.gen, e.x0_prev, e.starts, e.first_step);
+    const auto fn = e.record() ? (e.edit ? step_tail_kernel<true, true> : step_tail_kernel<false, true>)
+                               : (e.edit ? step_tail_kernel<true, false> : step_tail_kernel<false, false>);
+    hipLaunchKernelGGL(fn, dim3((M + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK), dim3(256), 0, s, x, xs, ng, nb, lat, e.coef, d_step, e.noise, pe,
+                       e.g, e.gs, e.cfg, B, T, e.gen, e.x0_prev, e.starts, e.first_step, e.traj_x, e.traj_x0, e.traj_counts);
     LADIFF_LAUNCH_CHECK();
     return 0;
 }

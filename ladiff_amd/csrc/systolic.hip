@@ -119,6 +119,8 @@ struct SysArgs {
     float* x0p;                           // multistep form: the previous step's data prediction, addressed like lat; null: the one-step rule (last: the other fields keep their kernarg offsets)
     const int32_t* starts;                // a loop from a source motion (the ED instantiations): [B] schedule position at which each prompt enters, or null: all at first_step
     int first_step;
+    float *trx, *trx0;                    // the denoising trajectory (the RC instantiations): [n,B,T,256] latents after each step / the step's data prediction, row step_lo + s; either may be null
+    const int32_t* trc;                   // [B] or null: rows t >= trc[b] are not recorded (StepEnd::traj_counts)
 };
 
 // In-kernel timeline (diagnostic twin build; the shipped library executes no stamp): s_memrealtime is one 100 MHz counter
@@ -1914,7 +1916,9 @@ struct SkipRole {
 // ED: a loop from a source motion (SysArgs::starts / first_step, step_gate in step_rule.h).  The pair's start travels like its scale (Pay::st,
 // loaded in `issue`, applied in `compute`); a frozen pair still stores latent + pe with the next step's parity for both branches, so the
 // hand-off sees no difference.  A template flag for the reason MS is one: see the register table of DESIGN 8h.
-template <int MR, int WS, int HO, bool MS = false, bool ED = false>
+// RC: the denoising trajectory (SysArgs::trx / trx0): `compute` stores the pair's l and m0 to row step_lo + s, unless the row lies past the
+// prompt's latent count (SysArgs::trc) (the 32-row plan carries those rows; the prologue zeroed them).  A template flag again: DESIGN 8k has the table.
+template <int MR, int WS, int HO, bool MS = false, bool ED = false, bool RC = false>
 struct TailRole {
     static constexpr int RT = 16 * MR, NW = 4 * WS, NQ = 16 / NW;        // (prompt, latent) pairs per wave: <= 16 per unit
     struct Geo { int lat[NQ], t[NQ], rc[NQ], pad[NQ]; };                // latent row, position, conditional-branch row of pair q; padding row of a slot without a pair
@@ -2043,6 +2047,13 @@ struct TailRole {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) xn[k] = l[k] + y.pe[i][k];
                 if (live) st4(p.lat + (size_t)g.lat[i] * D + c, l);
+                if constexpr (RC) {
+                    if (p.trc == nullptr || g.t[i] < p.trc[g.lat[i] / T]) {
+                        const size_t at = ((size_t)(p.step_lo + s) * p.B * T + g.lat[i]) * D + c;
+                        if (p.trx != nullptr) st4(p.trx + at, l);
+                        if (p.trx0 != nullptr) st4(p.trx0 + at, m0);
+                    }
+                }
                 const unsigned par = HO ? (unsigned)((s + 1) & TAG_MASK) : 0u;     // the input of the NEXT local step
                 st_out<HO>(st, rout, bu + q * 1024 + c * 4, xn, par);          // after the last step nobody reads it
                 st_out<HO>(st, rout, bc + g.rc[i] * 1024 + c * 4, xn, par);
@@ -2059,10 +2070,10 @@ struct TailRole {
 // blocks, and a unit's latents are read in `issue` and written in `compute` of the SAME unit one step earlier - with other
 // units in between, so a prefetch never overtakes the update it depends on as long as a tail owns more than one unit; with
 // one unit it does not prefetch.  The multistep form's x0_prev rows follow the same rule: read in `issue` (Pay::m1), written in `compute`.
-template <int MR, int WS, bool MS, bool ED>
-__device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, TailRole<MR, WS, 0, MS, ED>& r, Ctl* ctl) {
-    typename TailRole<MR, WS, 0, MS, ED>::Pay cur, nxt;
-    typename TailRole<MR, WS, 0, MS, ED>::Geo gcur, gnxt;
+template <int MR, int WS, bool MS, bool ED, bool RC>
+__device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, TailRole<MR, WS, 0, MS, ED, RC>& r, Ctl* ctl) {
+    typename TailRole<MR, WS, 0, MS, ED, RC>::Pay cur, nxt;
+    typename TailRole<MR, WS, 0, MS, ED, RC>::Geo gcur, gnxt;
     bool have = false;
     const int lane = threadIdx.x & 63, u0 = st.slice;
     const int nu = p.split ? p.NB / 2 : p.NB;
@@ -2073,7 +2084,7 @@ __device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, Tai
         return (const gu32*)flag_of(p, st.wait_group, b, 0) + (lane < st.wait_n ? lane : lane - st.wait_n) * FLAG_STRIDE;
     };
     r.prime(nu);
-    typename TailRole<MR, WS, 0, MS, ED>::Geo gnn;
+    typename TailRole<MR, WS, 0, MS, ED, RC>::Geo gnn;
     if (u0 < nu) { r.geo(u0, gcur); r.geo(u0 + NTAIL < nu ? u0 + NTAIL : u0, gnxt); gnn = gnxt; }
     for (int s = 0; s < p.n_steps; ++s)
         for (int u = u0; u < nu; u += NTAIL) {
@@ -2124,10 +2135,10 @@ __device__ __forceinline__ void tail_loop(const SysArgs& p, const Stage& st, Tai
 
 // Tagged hand-off: no barrier and no flag - every wave owns the (prompt, latent) pairs `wave + NW i` of its units, settles on the
 // two rows of each pair, updates the latents and stores the next step's input rows with the next step's parity.
-template <int MR, int WS, int HO, bool MS, bool ED>
-__device__ __forceinline__ void tail_loop_tag(const SysArgs& p, const Stage& st, TailRole<MR, WS, HO, MS, ED>& r) {
-    typename TailRole<MR, WS, HO, MS, ED>::Pay cur;
-    typename TailRole<MR, WS, HO, MS, ED>::Geo gcur, gnxt, gnn;
+template <int MR, int WS, int HO, bool MS, bool ED, bool RC>
+__device__ __forceinline__ void tail_loop_tag(const SysArgs& p, const Stage& st, TailRole<MR, WS, HO, MS, ED, RC>& r) {
+    typename TailRole<MR, WS, HO, MS, ED, RC>::Pay cur;
+    typename TailRole<MR, WS, HO, MS, ED, RC>::Geo gcur, gnxt, gnn;
     const int u0 = st.slice;
     const int nu = p.split ? p.NB / 2 : p.NB;
     r.prime(nu);
@@ -2169,7 +2180,8 @@ __device__ __forceinline__ void tail_loop_tag(const SysArgs& p, const Stage& st,
 // queue up (SysArgs::look_ahead); a kernel of its own, so that the other launches run exactly the code without it
 // MS = the TAIL stage runs the multistep form of the scheduler step (TailRole; SysArgs::x0p is set): kernels of their own as well
 // ED = the TAIL stage gates every pair by its prompt's start (a loop from a source motion; SysArgs::starts / first_step): likewise
-template <int MR, int AR, int WS, int HO, bool EQ = false, bool MS = false, bool ED = false>
+// RC = the TAIL stage records the denoising trajectory (SysArgs::trx / trx0): likewise
+template <int MR, int AR, int WS, int HO, bool EQ = false, bool MS = false, bool ED = false, bool RC = false>
 __global__ __launch_bounds__(256 * WS, 1) void systolic_loop_kernel(const SysArgs p) {
     static_assert(WS == 1 || MR == 1, "two waves per SIMD: 16-row blocks only (the reduce parts' slot tables hold 12 slots: wave + 8 q needs q < 1)");
     // all LDS is dynamic (a static variable would shift the dynamic base off its 16-byte alignment, cdna_hip_programming.md G17)
@@ -2259,7 +2271,7 @@ __global__ __launch_bounds__(256 * WS, 1) void systolic_loop_kernel(const SysArg
         case R_SKIP: with_ho([&](auto hc) { SkipRole<MR, AR, WS, decltype(hc)::value> r(p, st, lds); run(r); }); break;
         case R_TAIL:
             with_ho([&](auto hc) {
-                TailRole<MR, WS, decltype(hc)::value, MS, ED> r(p, st, lds);
+                TailRole<MR, WS, decltype(hc)::value, MS, ED, RC> r(p, st, lds);
                 if constexpr (HO) tail_loop_tag(p, st, r);
                 else tail_loop(p, st, r, ctl);
             });
@@ -2329,6 +2341,7 @@ struct LoopKernel { LoopKey key; void (*fn)(const SysArgs); };      // launched 
 #define LOOP_KERNEL(AR, MR, WS, HO, EQ) {{MR, WS, HO == 1, EQ, AR == 1, false, false}, systolic_loop_kernel<MR, AR, WS, HO, EQ>}
 #define LOOP_KERNEL_MS(AR, MR, WS, HO, EQ) {{MR, WS, HO == 1, EQ, AR == 1, true, false}, systolic_loop_kernel<MR, AR, WS, HO, EQ, true>}
 #define LOOP_KERNEL_ED(AR, MR, WS, HO, EQ, MS) {{MR, WS, HO == 1, EQ, AR == 1, MS, true}, systolic_loop_kernel<MR, AR, WS, HO, EQ, MS, true>}
+#define LOOP_KERNEL_RC(AR, MR, WS, HO, MS) {{MR, WS, HO == 1, false, AR == 1, MS, false, true}, systolic_loop_kernel<MR, AR, WS, HO, false, MS, false, true>}
 const LoopKernel LOOP_KERNELS[] = {
     // flags: 16-row blocks with two waves per SIMD (ladiff_debug_set_handoff(0)) and 32-row blocks, split | fp32
     LOOP_KERNEL(0, 1, 2, 0, false), LOOP_KERNEL(0, 2, 1, 0, false), LOOP_KERNEL(1, 1, 2, 0, false), LOOP_KERNEL(1, 2, 1, 0, false),
@@ -2344,10 +2357,15 @@ const LoopKernel LOOP_KERNELS[] = {
     LOOP_KERNEL_ED(1, 1, 2, 1, false, false), LOOP_KERNEL_ED(0, 1, 2, 1, true, false), LOOP_KERNEL_ED(1, 1, 2, 1, true, false),
     LOOP_KERNEL_ED(0, 2, 1, 0, false, true), LOOP_KERNEL_ED(1, 2, 1, 0, false, true), LOOP_KERNEL_ED(0, 1, 2, 1, false, true),
     LOOP_KERNEL_ED(1, 1, 2, 1, false, true), LOOP_KERNEL_ED(0, 1, 2, 1, true, true), LOOP_KERNEL_ED(1, 1, 2, 1, true, true),
+    // a loop from noise that records its trajectory (traj_x / traj_x0 set): 32-row blocks and tagged 16-row blocks without look-ahead
+    // (sys_launch_policy), one-step and multistep.  A recording loop from a source motion runs as step graphs (reverse.hip)
+    LOOP_KERNEL_RC(0, 2, 1, 0, false), LOOP_KERNEL_RC(1, 2, 1, 0, false), LOOP_KERNEL_RC(0, 1, 2, 1, false), LOOP_KERNEL_RC(1, 1, 2, 1, false),
+    LOOP_KERNEL_RC(0, 2, 1, 0, true), LOOP_KERNEL_RC(1, 2, 1, 0, true), LOOP_KERNEL_RC(0, 1, 2, 1, true), LOOP_KERNEL_RC(1, 1, 2, 1, true),
 };
 #undef LOOP_KERNEL
 #undef LOOP_KERNEL_MS
 #undef LOOP_KERNEL_ED
+#undef LOOP_KERNEL_RC
 }  // namespace
 
 int sys_reset_status(float* ws, hipStream_t s) {
@@ -2362,7 +2380,7 @@ int sys_reset_status(float* ws, hipStream_t s) {
 int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, const float* tkv, const float* ctab, int n_ctab, float* lat,
                          const int32_t* counts, const StepEnd& e, int B, int T, int step_lo, int n, int fp32, int MR, int NB, hipStream_t s,
                          int fault_wg, unsigned long long timeout_ticks) {
-    const LoopLaunch p = sys_launch_policy(MR, NB, fp32 != 0, e.x0_prev != nullptr, e.edit, g_loop.snapshot());
+    const LoopLaunch p = sys_launch_policy(MR, NB, fp32 != 0, e.x0_prev != nullptr, e.edit, g_loop.snapshot(), e.record());
     const LoopKernel* k = nullptr;
     for (const LoopKernel& c : LOOP_KERNELS) if (c.key == p.key) k = &c;
     if (k == nullptr) return LADIFF_ERR_UNSUPPORTED;       // before anything is enqueued
@@ -2373,7 +2391,7 @@ int launch_systolic_loop(const DenoiserW& W, float* ws, const float* tables, con
     a.flags = reinterpret_cast<unsigned*>(ws + L.off_flags);
     a.status = reinterpret_cast<unsigned*>(ws + L.off_status);
     a.tables = tables; a.tkv = tkv; a.ctab = ctab; a.coef = e.coef; a.noise = e.noise; a.pe = W.query_pe; a.ng = W.norm.g; a.nb = W.norm.b;
-    a.lat = lat; a.x0p = e.x0_prev; a.starts = e.starts; a.first_step = e.first_step; a.counts = counts; a.gscale = e.g; a.gscales = e.gs; a.B = B; a.B2 = e.cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
+    a.lat = lat; a.x0p = e.x0_prev; a.starts = e.starts; a.first_step = e.first_step; a.trx = e.traj_x; a.trx0 = e.traj_x0; a.trc = e.traj_counts; a.counts = counts; a.gscale = e.g; a.gscales = e.gs; a.B = B; a.B2 = e.cfg ? 2 * B : B; a.T = T; a.P = 0; a.NB = NB; a.step_lo = step_lo; a.n_steps = n;
     a.n_ctab = n_ctab; a.gen = e.gen;
     a.split = e.cfg ? L.split : 0;     // no guidance: every block is a unit of its own (sys_pack_blocks)
     // fault_wg / timeout_ticks: the caller's SAMPLER's fault injection (ladiff_sampler_set_fault; -1 / 0 = none / default bound)

@@ -115,12 +115,14 @@ struct LoopSwitchAtoms {
 extern LoopSwitchAtoms g_loop;
 inline RedPlan red_plan(int MR) { return MR != 1 ? PLAN32 : g_loop.stage_plan == 1 ? PLAN16_OUT2 : PLAN16; }
 // sys_launch_policy's result: the key of the kernel instantiation (the rows of LOOP_KERNELS, systolic.hip) and the policy words of SysArgs
-struct LoopKey { int mr, waves; bool tagged, look_ahead, fp32, multistep, edit; };   // mr: 1 | 2 = 16- | 32-row blocks (one form); waves per SIMD; look-ahead only with the tagged hand-off
+struct LoopKey { int mr, waves; bool tagged, look_ahead, fp32, multistep, edit, record = false; };   // mr: 1 | 2 = 16- | 32-row blocks (one form); waves per SIMD; look-ahead only with the tagged hand-off
 inline bool operator==(const LoopKey& a, const LoopKey& b) {
-    return a.mr == b.mr && a.waves == b.waves && a.tagged == b.tagged && a.look_ahead == b.look_ahead && a.fp32 == b.fp32 && a.multistep == b.multistep && a.edit == b.edit;
+    return a.mr == b.mr && a.waves == b.waves && a.tagged == b.tagged && a.look_ahead == b.look_ahead && a.fp32 == b.fp32 && a.multistep == b.multistep && a.edit == b.edit && a.record == b.record;
 }
 struct LoopLaunch { LoopKey key; int look_ahead, pace, delay_mask, delay_len, pause_mask, pause_len, force_mismatch; };
-LoopLaunch sys_launch_policy(int MR, int NB, bool fp32, bool multistep, bool edit, const LoopSwitches& sw);
+// record: the call records its trajectory (the RC rows of LOOP_KERNELS): those have no look-ahead form, so a tagged recording launch runs
+// without look-ahead whatever its block count
+LoopLaunch sys_launch_policy(int MR, int NB, bool fp32, bool multistep, bool edit, const LoopSwitches& sw, bool record = false);
 
 struct SysLayout {
     size_t blk, ring;             // floats of one [NB][RT][256] buffer / of one [PRING][RT][256] partial plane

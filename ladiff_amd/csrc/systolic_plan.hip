@@ -305,13 +305,14 @@ void choose_plan(int B, int T, const int32_t* h_counts, bool masked, int loop_mo
     else { plan.swap(p32); *plan_mr = 2; *plan_nb = nb32; }
 }
 
-LoopLaunch sys_launch_policy(int MR, int NB, bool fp32, bool multistep, bool edit, const LoopSwitches& sw) {
+LoopLaunch sys_launch_policy(int MR, int NB, bool fp32, bool multistep, bool edit, const LoopSwitches& sw, bool record) {
     const int la_from = sw.look_ahead_from >= 0 ? sw.look_ahead_from : LOOK_AHEAD_BLOCKS;      // ladiff_debug_set_loop_thresholds
     const int small_upto = sw.small_upto >= 0 ? sw.small_upto : SMALL_LAUNCH_BLOCKS;
     LoopLaunch p;
     p.look_ahead = NB >= la_from ? 1 : 0;               // whether tagged or not
     const bool tagged = MR == 1 && sw.waves16 == 2 && sw.handoff == 1;
-    p.key = LoopKey{MR == 1 ? 1 : 2, MR == 1 && sw.waves16 == 2 ? 2 : 1, tagged, tagged && p.look_ahead, fp32, multistep, edit};
+    if (record && tagged) p.look_ahead = 0;             // the recording instantiations: none with look-ahead
+    p.key = LoopKey{MR == 1 ? 1 : 2, MR == 1 && sw.waves16 == 2 ? 2 : 1, tagged, tagged && p.look_ahead, fp32, multistep, edit, record};
     p.pause_mask = sw.poll_pause & 0xff; p.pause_len = (sw.poll_pause >> 8) & 0xff; p.force_mismatch = sw.xcd_local == 2 ? 1 : 0;
     p.pace = sw.pace >= 0 ? sw.pace : (NB <= small_upto ? 0 : (4 | (4 << 8)));
     // Small launches (a block's trip through the stages bounds the step, the stages wait for rows most of the time): the LIN and FFN

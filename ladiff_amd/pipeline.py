@@ -71,7 +71,15 @@ def remove_padding(tensors, lengths):
     return [t[:l] for t, l in zip(tensors, lengths)]
 
 
+TRAJECTORY_KINDS = ("latents", "x0", "both")      # what `_diffusion_reverse(trajectory=...)` records
+
+
 class LADIFF(nn.Module):
+    # a recorded trajectory costs n x B x T KiB per kind (DDPM-1000 with 128 prompts: 655 MB): larger requests are refused by name
+    max_trajectory_bytes = 1 << 30
+    # samples per `vae.decode` of `decode_trajectory` (8 x the headline batch; the decoder itself sets no limit)
+    trajectory_decode_samples = 1024
+
     def __init__(self, cfg=None, datamodule=None, *, denoiser=None, vae=None, scheduler=None, text_encoder=None,
                  guidance_scale=None, num_inference_timesteps=None, eta=None, max_it=None, frame_per_latent=None,
                  test_efficiency=None, use_graph=True, precision=None, loop="pipeline", fallback=False,
@@ -290,11 +298,12 @@ class LADIFF(nn.Module):
         except Exception:
             pass
 
-    def _get_plan(self, B, T, n_steps, eta, dev, n_text=1):
+    def _get_plan(self, B, T, n_steps, eta, dev, n_text=1, trajectory=None):
         """Persistent device buffers + scheduler tables + sampler for one (B, T, schedule): hipGraph kernel nodes bake
-        pointers in, and the per-step scalar tables are built once, not per call."""
+        pointers in, and the per-step scalar tables are built once, not per call.  A recording call (`trajectory`) has a plan of its
+        own per kind: its graphs hold the trajectory buffers, so calls with and without never capture each other's graphs again."""
         sch = self.scheduler
-        key = (B, T, n_steps, float(eta), str(dev), id(sch), n_text)
+        key = (B, T, n_steps, float(eta), str(dev), id(sch), n_text) + (() if trajectory is None else (trajectory,))
         plan = self._plans.get(key)
         if plan is not None:
             self._plans[key] = self._plans.pop(key)          # most recently used last
@@ -327,6 +336,10 @@ class LADIFF(nn.Module):
             "tables_key": None,      # weights the time tables inside `ws` were built from
             "sampler": None,
         }
+        # the recorded trajectory [n,B,T,256] per kind (the layout of step_noise): plan-owned, new values replay the graphs
+        for name, kinds in (("traj_x", ("latents", "both")), ("traj_x0", ("x0", "both"))):
+            if trajectory in kinds:
+                plan[name] = torch.empty(n_steps, B, T, 256, dtype=torch.float32, device=dev)
         if getattr(sch, "multistep", False):
             # the previous step's data prediction of a multistep scheduler: the loop reads it only at steps whose row uses it (never
             # at step 0), so it is neither cleared nor copied between calls; every launch of this plan runs the multistep entry
@@ -460,7 +473,7 @@ class LADIFF(nn.Module):
 
     def _diffusion_reverse(self, encoder_hidden_states, lengths=None, init_noise=None, step_noise=None, noise_seed=None, *,
                            guidance_scale=None, seeds=None, prompt_index=None, source_latents=None, strength=None, start_steps=None,
-                           first_step=None):
+                           first_step=None, trajectory=None):
         """text_emb [2B,1,768] (unconditional half first), lengths list[int] -> z [max_it, B, 256]  (ladiff.py:333-571).
         Stochastic schedules (DDPM, eta > 0): `step_noise` [n,B,T,256] if given; otherwise the noise is drawn on the device where it
         is consumed (csrc/noise_gen.h) from `noise_seed` (default: a seed taken from torch's CPU generator, so torch.manual_seed makes
@@ -481,8 +494,26 @@ class LADIFF(nn.Module):
         or `start_steps` (B positions) says where; the loop runs positions min(starts) .. n - 1 and a prompt that starts later keeps its
         latents until then.  `init_noise` (or the prompts' keys at position -1) is the noise that is added; `init_noise_sigma` is not.
         `first_step` (optional) is the first position the launches run instead of min(starts) - it must not exceed it; given alone,
-        without strength or start_steps, every prompt starts there and the loop takes no array."""
+        without strength or start_steps, every prompt starts there and the loop takes no array.
+
+        `trajectory` = "latents" | "x0" | "both" records the loop and returns (z, traj): traj["latents"][s] are the
+        latents after position first_step + s (`scheduler.step(...).prev_sample`; the last row is z), traj["x0"][s] that step's data
+        prediction (`pred_original_sample`), each [n_run,T,B,256] with n_run = n - first_step, rows past a prompt's latent count exact
+        zeros; traj["first_step"] is 0 unless the call is an edit.  While a prompt of an edit has not entered the schedule its "latents"
+        rows hold the noised source and its "x0" rows zeros.  Recording changes no bit of z.  The size is checked against
+        `max_trajectory_bytes` first."""
         dev = encoder_hidden_states.device
+        if trajectory is not None:
+            if trajectory not in TRAJECTORY_KINDS:
+                raise ValueError(f"trajectory {trajectory!r}: expected None, " + ", ".join(repr(k) for k in TRAJECTORY_KINDS))
+            if self.test_efficiency:
+                raise NotImplementedError("a recorded trajectory with test_efficiency is not built")
+            if int(encoder_hidden_states.shape[1]) != 1:
+                raise NotImplementedError("a recorded trajectory with a text sequence (n_text > 1) is not built")
+            size = (2 if trajectory == "both" else 1) * int(self.num_inference_timesteps) * len(lengths) * self.max_it * 1024
+            if size > self.max_trajectory_bytes:
+                raise ValueError(f"a trajectory of {size} bytes ({trajectory!r}: {self.num_inference_timesteps} steps x {len(lengths)} prompts x "
+                                 f"{self.max_it} latents, 1 KiB each) exceeds max_trajectory_bytes = {self.max_trajectory_bytes}")
         starts = None
         if source_latents is not None:
             n_sched = int(self.num_inference_timesteps)
@@ -525,9 +556,11 @@ class LADIFF(nn.Module):
             noise_seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         self.last_noise_seed = None if step_noise is not None or noise_seed is None else int(noise_seed)
         first = int(self.noise_first_prompt)
+        if trajectory is not None and source_latents is not None and first_step is None:
+            first_step = min(starts)                      # one first position for every chunk: their records are concatenated
         if len(spans) == 1:
             return self._reverse_one(encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed, first, per,
-                                     source_latents, starts, first_step)
+                                     source_latents, starts, first_step, trajectory)
         # prompts are independent (attention is per sample, guidance pairs the two branches of one prompt): a large batch is
         # several launches of the loop on contiguous prompt ranges, the noise drawn for the whole batch and sliced
         if init_noise is None and seeds is None:
@@ -540,11 +573,16 @@ class LADIFF(nn.Module):
                                         None if init_noise is None else init_noise[lo:hi],
                                         None if step_noise is None else step_noise[:, lo:hi], noise_seed, first + lo, part,
                                         None if source_latents is None else source_latents[:, lo:hi], None if starts is None else starts[lo:hi],
-                                        first_step))
-        return torch.cat(zs, dim=1)
+                                        first_step, trajectory))
+        if trajectory is None:
+            return torch.cat(zs, dim=1)
+        trajs = [t for _, t in zs]                        # [n_run,T,B,256] per chunk: along B
+        traj = {k: torch.cat([t[k] for t in trajs], dim=2) for k in trajs[0] if k != "first_step"}
+        traj["first_step"] = trajs[0]["first_step"]
+        return torch.cat([z for z, _ in zs], dim=1), traj
 
     def _reverse_one(self, encoder_hidden_states, lengths, counts, T, init_noise, step_noise, noise_seed=None, first_prompt=0, per=None,
-                     source=None, starts=None, first_step=None):
+                     source=None, starts=None, first_step=None, trajectory=None):
         """One launch sequence of the loop on B prompts: prologue graph, N steps (pipeline kernel or step graphs), final masking."""
         L = _lib.lib()
         dev = encoder_hidden_states.device
@@ -553,7 +591,7 @@ class LADIFF(nn.Module):
         dup = 2 if cfg else 1
         B = len(lengths)
         sch = self.scheduler
-        plan = self._get_plan(B, T, self.num_inference_timesteps, self.eta, dev, n_text)
+        plan = self._get_plan(B, T, self.num_inference_timesteps, self.eta, dev, n_text, trajectory)
         self._last.append(plan)
         n, need_noise = plan["n"], plan["need_noise"]
         if source is not None and max(starts if starts is not None else [first_step]) >= n:
@@ -608,6 +646,12 @@ class LADIFF(nn.Module):
                 entry = L.ladiff_diffusion_reverse_from
                 tail = (None if x0_prev is None else _lib.ptr(x0_prev), _lib.ptr(plan["z0"]), None if starts is None else plan["starts"].data_ptr(), first_step,
                         run.cuda_stream)
+            if trajectory is not None:                                # a recording call, edit or not: the one entry that takes the buffers
+                entry = L.ladiff_diffusion_reverse_record
+                edit_args = tail[1:4] if source is not None else (None, None, 0)
+                tail = (None if x0_prev is None else _lib.ptr(x0_prev), *edit_args,
+                        _lib.ptr(plan["traj_x"]) if "traj_x" in plan else None, _lib.ptr(plan["traj_x0"]) if "traj_x0" in plan else None,
+                        run.cuda_stream)
             _lib.check(entry(
                 sampler, wt.array,
                 wt.split_array() if _lib.is_split(self.precision) else None, wt.generation, _lib.ptr(plan["text"]),
@@ -656,7 +700,13 @@ class LADIFF(nn.Module):
                     self.check()
         if run is not cur:
             cur.wait_stream(run)
-        return plan["z"].clone()
+        if trajectory is None:
+            return plan["z"].clone()
+        # cloned out as z is, in z's layout per position ([n,B,T,256] -> [n_run,T,B,256]); the rows before first_step were not written
+        traj = {kind: plan[name][first_step:n].permute(0, 2, 1, 3).contiguous() for kind, name in (("latents", "traj_x"), ("x0", "traj_x0"))
+                if name in plan}
+        traj["first_step"] = first_step
+        return plan["z"].clone(), traj
 
     @staticmethod
     def noise_tensor(seed, n_steps, B, T, first_prompt=0, first_step=0, device="cuda:0", seeds=None, prompt_index=None):
@@ -732,24 +782,85 @@ class LADIFF(nn.Module):
 
     # ------------------------------------------------------------------ callers' surface
     def sample(self, text_emb, lengths, init_noise=None, step_noise=None, check=True, noise_seed=None, *, guidance_scale=None, seeds=None,
-               prompt_index=None, source_latents=None, strength=None, start_steps=None, return_att_maps=False):
+               prompt_index=None, source_latents=None, strength=None, start_steps=None, return_att_maps=False, trajectory=None):
         """text embeddings -> (z [max_it,B,256], feats [B,max(len),nfeats]): ladiff.py:266 + :283.  Returns checked frames: the
         decode is queued, then the host waits for the loop's status words (LadiffHipError if the loop was abandoned).
         check=False skips the wait (the host may then queue a call ahead) - the caller owes a `check()` before using the frames.
         guidance_scale / seeds / prompt_index: one value per prompt, see `_diffusion_reverse`.
         source_latents with strength or start_steps: an edit of those latents instead of a sample from noise, see there.
-        return_att_maps=True -> (z, feats, maps): the decoder's cross-attention weights [9,B,F,max_it] of that z (`LADiffVae.decode`)."""
+        return_att_maps=True -> (z, feats, maps): the decoder's cross-attention weights [9,B,F,max_it] of that z (`LADiffVae.decode`).
+        trajectory="latents" | "x0" | "both" appends the loop's record `traj` (see `_diffusion_reverse`) to what is returned."""
         edit = {} if source_latents is None and strength is None and start_steps is None else \
             {"source_latents": source_latents, "strength": strength, "start_steps": start_steps}
         z = self._diffusion_reverse(text_emb, lengths, init_noise=init_noise, step_noise=step_noise, noise_seed=noise_seed,
-                                    guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index, **edit)
+                                    guidance_scale=guidance_scale, seeds=seeds, prompt_index=prompt_index,
+                                    **({} if trajectory is None else {"trajectory": trajectory}), **edit)
+        traj = ()
+        if trajectory is not None:
+            z, traj = z[0], (z[1],)
         if return_att_maps:
             feats, maps = self.vae.decode(z, lengths, return_att_maps=True)
         else:
             feats = self.vae.decode(z, lengths)
         if check:
             self.check()
-        return (z, feats, maps) if return_att_maps else (z, feats)
+        return ((z, feats, maps) if return_att_maps else (z, feats)) + traj
+
+    def _diffusion_reverse_tsne(self, encoder_hidden_states, lengths=None):
+        """The reference's name (ladiff.py:573-743): the latents after every step, concatenated over the steps -> [n * max_it, B, 256]."""
+        _, traj = self._diffusion_reverse(encoder_hidden_states, lengths, trajectory="latents")
+        rows = traj["latents"]
+        return rows.reshape(rows.shape[0] * rows.shape[1], rows.shape[2], 256)
+
+    def decode_trajectory(self, rows, lengths, steps=None):
+        """Rows of a recorded trajectory [S,T,B,256] (`traj["latents"]` or `traj["x0"]`; `steps`: the subset of its positions to take,
+        default all) -> frames [S', B, max(lengths), nfeats]: one `vae.decode` of S' x B samples, cut into decodes of at most
+        `trajectory_decode_samples` samples (whole positions) beyond that."""
+        lengths = [int(l) for l in lengths]
+        if rows.dim() != 4 or rows.shape[2] != len(lengths) or rows.shape[3] != 256:
+            raise ValueError(f"rows {tuple(rows.shape)}: expected [S,T,B,256] for {len(lengths)} lengths")
+        if steps is not None:
+            steps = [int(s) for s in steps]
+            if any(not -rows.shape[0] <= s < rows.shape[0] for s in steps):
+                raise ValueError(f"steps {steps} outside a trajectory of {rows.shape[0]} positions")
+            rows = rows[steps]
+        S, T, B = int(rows.shape[0]), int(rows.shape[1]), len(lengths)
+        per = max(1, int(self.trajectory_decode_samples) // B)            # positions per decode
+        out = []
+        with torch.no_grad():
+            for lo in range(0, S, per):
+                part = rows[lo:lo + per]
+                z = part.permute(1, 0, 2, 3).reshape(T, part.shape[0] * B, 256)      # sample k * B + b = position k, prompt b
+                feats = self.vae.decode(z, lengths * int(part.shape[0]))
+                out.append(feats.reshape(part.shape[0], B, feats.shape[1], feats.shape[2]))
+        return out[0] if len(out) == 1 else torch.cat(out, dim=0)
+
+    def preview(self, batch, steps=None, kind="x0"):
+        """`forward` with the loop recorded: (joints, previews) - joints what `forward` returns, previews[k][b] the [L_b,22,3] joints of
+        prompt b decoded from the `kind` ("x0": the step's data prediction, "latents": the latents after it) row of position steps[k]
+        (default: every position).  The film of a motion taking shape."""
+        if kind not in ("x0", "latents"):
+            raise ValueError(f"kind {kind!r}: expected 'x0' or 'latents'")
+        texts, lengths = batch["text"], [int(l) for l in batch["length"]]
+        if self.text_encoder is None or (self.feats2joints is None and self.feats2joints_device is None):
+            raise RuntimeError("LADIFF.preview needs a text_encoder callable and datamodule.feats2joints")
+        self._check_loaded_weights()
+        start = time.time()
+        text_emb = self.text_encoder(self._guided_texts(texts))
+        per = {kw: batch[key] for key, kw in (("guidance_scale", "guidance_scale"), ("seed", "seeds")) if batch.get(key) is not None}
+        z, traj = self._diffusion_reverse(text_emb, lengths, trajectory=kind, **per)
+        f2j = self.feats2joints_device or (lambda f: self.feats2joints(f.detach().cpu()))
+        with torch.no_grad():
+            joints = f2j(self.vae.decode(z, lengths).detach())
+            frames = self.decode_trajectory(traj[kind], lengths, steps)
+            S, B = int(frames.shape[0]), len(lengths)
+            film = f2j(frames.reshape(S * B, frames.shape[2], frames.shape[3]).detach())
+        torch.cuda.synchronize()
+        self.check()
+        self.times.append(time.time() - start)
+        film = film.cpu()
+        previews = [remove_padding(film[k * B:(k + 1) * B], lengths) for k in range(S)]
+        return remove_padding(joints.cpu(), lengths), previews
 
     def forward(self, batch, latentwise_gen=None, plot_att_map=None):
         texts, lengths = batch["text"], batch["length"]
