@@ -760,7 +760,8 @@ def test_test_diffusion_forward_rs_set(denoiser, vae):
 
 def test_bf16_pair_flavour_of_the_library():
     """libladiff_hip_bf16.so (fp32's exponent range, 16-bit operands: `_lib.select_split_format("bf16")`, one format per process) samples
-    within the gate as well; run in a child process of its own."""
+    within the gate as well; run in a child process of its own.  This is the check of `select_split_format` and of
+    LADIFF(precision="bf16x3"); the library's kernels are held to the oracle family by family in tests/test_gpu_bf16_flavour.py."""
     import subprocess, sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "bf16_flavour_check.py")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "split format 0 (bf16x3)" in r.stdout, (r.stdout + r.stderr)[-800:]

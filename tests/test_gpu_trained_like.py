@@ -59,6 +59,10 @@ def check(name, precision, got, want, e32, gate=None):
     # fp32 evaluation of the oracle already misses it (the guided loop on peaked weights amplifies rounding: e32 of the frames reaches
     # 1e-2 at 43 prompts), the gate says nothing about a kernel
     if gate is not None and want.abs().max().item() < 16 and 8 * e32 < gate:
+        # the gate is a number for fp16 pairs (2^-21 per operand); in split mode on the bf16-pair build (2^-16) it is 32 x that, the
+        # ratio of the two terms of trained_like.bound (measured there: 1.0e-3 ... 1.5e-3 on three decodes, profiles/bf16_suite)
+        if precision != "fp32" and lib().ladiff_split_format() == 0:
+            gate = 32 * gate
         assert err < gate, (name, precision, err)
     return err
 
