@@ -745,6 +745,74 @@ LADIFF_API int ladiff_joint_ape_ave(const float* joints_rst, const float* joints
 LADIFF_API int ladiff_joint_mr(const float* joints_rst, const float* joints_ref, const int32_t* h_lengths, int B, int F, int J,
                     float* seq_rows, double* acc, ladiff_stream_t stream);
 
+/* ------------------------------------------------------------------ motion renderer (csrc/render.hip)
+ * Joint positions to pictures: a stick figure in the style of the reference's plot_3d_motion (data/humanml/utils/plot_script.py; the
+ * end of demo.py) - five coloured kinematic chains over a grey ground rectangle on a plain background.  It does NOT reproduce
+ * matplotlib's pixels: the image model below is this library's own, and it is what tests/render_ref.py restates and the tests hold the
+ * kernels to.
+ *
+ * Inputs   joints [B,L,J,3] fp32.  J = 22: the chains of t2m_kinematic_chain, J = 21: kit_kinematic_chain (utils/paramUtil.py):
+ *            t2m  {0,2,5,8,11} {0,1,4,7,10} {0,3,6,9,12,15} {9,14,17,19,21} {9,13,16,18,20}
+ *            kit  {0,11,12,13,14,15} {0,16,17,18,19,20} {0,1,2,3,4} {3,5,6,7} {3,8,9,10}
+ *          a bone joins two consecutive joints of a chain.  h_lengths: HOST int32 [B], 1 <= h_lengths[b] <= L <= 256.
+ *          16 <= H, W <= 1024, W % 4 == 0.
+ * Scene    per motion, over its own frames t < h_lengths[b] only: mins / maxs = the component-wise minimum / maximum over all joints of
+ *          those frames.  Every y is shifted by -mins.y (the lowest point touches the ground y = 0).  "Root" is joint 0.
+ * Camera   a pinhole look-at camera.  Target T = (0, target_height, 0); with el = elev_deg, az = azim_deg (degrees) and a distance d,
+ *          eye E = T + d (cos el sin az, sin el, cos el cos az); f = normalize(T - E), r = normalize(f x (0,1,0)), u = r x f;
+ *          F = focal H / 2 pixels.  A point P has dv = P - E, depth zc = dv.f, and the screen position sx = W/2 + F (dv.r) / zc,
+ *          sy = H/2 - F (dv.u) / zc.  The centre of pixel (row i, column j) is (j + 0.5, i + 0.5).  |el| < 90 and E.y > 0 (at d = dist)
+ *          are required.  f, r, u do not depend on d.
+ * frames   (mode LADIFF_RENDER_FRAMES) one image per rendered frame: out [B, ceil(L / frame_stride), H, W, 3]; image (b, i) shows
+ *          frame t = i frame_stride.  t >= h_lengths[b]: the whole image is the background colour.  Otherwise the pose is frame t with
+ *          x and z reduced by the root's x and z at t; the ground rectangle at y = 0 is x in [mins.x - root_x(t), maxs.x - root_x(t)],
+ *          z likewise; d = dist; one pose of opacity 1.
+ * strip    (mode LADIFF_RENDER_STRIP) one image per motion: out [B, H, W, 3].  With len = h_lengths[b], n = min(n_poses, len), the
+ *          poses are the frames t_k = (k (len - 1) + (n - 1) / 2) / (n - 1) in integer division, k = 0 .. n-1 (n = 1: t_0 = 0); x and z
+ *          are reduced by the centre (mins + maxs) / 2 of the bounding box; the ground is the bounding rectangle grown by
+ *          ground_margin on every side; pose k has opacity a_k = alpha_min + (1 - alpha_min) (k / (n - 1)) (n = 1: 1); the camera
+ *          distance is d = dist max(1, extent / strip_fit), extent = max(maxs.x - mins.x, maxs.z - mins.z), computed on the device.
+ * Pixel    c = background; then, in this fixed order, c <- c (1 - q) + colour q with q = opacity x cov: the ground (opacity
+ *          ground_alpha, colour ground_rgb), then the poses in time order, the chains in table order, the bones in chain order (colour
+ *          chain_rgb[chain]).  No depth sort: a fixed order is continuous in the input.
+ * Bone     skipped unless both endpoints have zc > near.  With the screen endpoints A, B, e = B - A and the pixel centre p:
+ *          s = clamp(((p - A).e) / max(e.e, 1e-12), 0, 1), dist2d = |p - (A + s e)|, cov = clamp(0.5 + line_width / 2 - dist2d, 0, 1):
+ *          a one-pixel linear edge; line_width in pixels.  A zero-length bone is a dot; nothing is NaN.
+ * Ground   by ray: D = f + cx r + cy u, cx = (px - W/2) / F, cy = -(py - H/2) / F.  D.y >= 0: cov = 0.  Otherwise th = -E.y / D.y, the
+ *          hit point (hx, hz) = (E.x + th D.x, E.z + th D.z), sd = min(hx - x0, x1 - hx, hz - z0, z1 - hz) for the rectangle
+ *          [x0,x1] x [z0,z1], cov = clamp(0.5 + sd F / th, 0, 1).  The rectangle is bounded, so cov -> 0 towards the horizon.
+ * Output   fp32 c in [0,1] (out_is_float != 0) or uint8 floor(255 c + 0.5).
+ * Defaults (ladiff_amd/render.py; nothing tests them): background white, ground (0.5, 0.5, 0.5) with ground_alpha 0.5, chain colours
+ *          #DD5A37 #D69E00 #B75A39 #DD5A37 #D69E00 (the first five of the reference's list), line_width = H / 54 (the reference's 4 pt on
+ *          a 3 in x 100 dpi figure), elev_deg 15, azim_deg 25, dist 3.6, focal 2, target_height 0.9, near 0.1, ground_margin 0.5,
+ *          alpha_min 0.25, strip_fit 3: a standing HumanML3D figure (about 1.7 units tall) fills roughly the middle half of a square image.
+ *
+ * Two kernels, both fp32 in every build flavour.  The scene kernel (one workgroup per motion, no atomics) writes a per-motion record -
+ * bounds, length, strip pose indices, fitted distance - to the workspace, which holds nothing else
+ * (ladiff_render_workspace_bytes(B), non-decreasing in B).  The raster kernel (64 x 16 pixel tiles x images) projects its image's pose
+ * into LDS, culls the bones against its tile and composites; a thread owns four horizontally adjacent pixels and stores 12 (uint8) or 48
+ * (fp32) contiguous bytes; out is write-only and every element is written; an image past its motion's length does no scene work.  The
+ * bits of an image depend on its own motion only (a motion of a ragged batch gives the bytes it gives alone).  The camera basis is
+ * computed on the host in double and rounded once; the entry neither allocates, copies nor synchronises (the lengths travel in the
+ * scene kernel's arguments, one launch pair per 1024 motions) and is capturable.
+ * Errors, all before any GPU work: njoints outside {21, 22} -> LADIFF_ERR_UNSUPPORTED; LADIFF_ERR_ARG for a NULL joints / h_lengths /
+ * params / out / ws, B < 0, a mode other than the two, n_poses < 1, frame_stride < 1, |elev_deg| >= 90, E.y <= 0, a non-positive dist,
+ * focal, line_width, near_plane or strip_fit, a negative ground_margin, or an opacity or colour component outside [0, 1];
+ * LADIFF_ERR_SHAPE for L outside [1, 256], H or W outside [16, 1024], W % 4 != 0, a length outside [1, L], joints or ws not aligned to
+ * 4 bytes, out not aligned to 4 (uint8) or 16 (fp32) bytes; LADIFF_ERR_WORKSPACE for ws_bytes below the query.  B == 0 does nothing. */
+enum { LADIFF_RENDER_FRAMES = 0, LADIFF_RENDER_STRIP = 1 };
+typedef struct ladiff_render_params {
+    float elev_deg, azim_deg, dist, focal, target_height, near_plane;
+    float line_width;                 /* pixels */
+    float ground_margin, alpha_min, strip_fit, ground_alpha;
+    float background_rgb[3], ground_rgb[3], chain_rgb[5][3];
+    int32_t frame_stride;             /* frames mode: every frame_stride-th frame is rendered (1 = all); ignored by the strip */
+} ladiff_render_params;
+LADIFF_API size_t ladiff_render_workspace_bytes(int B);
+LADIFF_API int ladiff_render_motion(const float* joints, const int32_t* h_lengths, int B, int L, int njoints,
+                         const ladiff_render_params* params, int mode, int n_poses, int H, int W, void* out, int out_is_float, void* ws,
+                         size_t ws_bytes, ladiff_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

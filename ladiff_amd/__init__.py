@@ -5,6 +5,7 @@ the `LADIFF`-compatible loop owner.  Arithmetic: libladiff_hip.so (ladiff_amd/cs
 """
 from .feats2joints import Feats2Joints                   # noqa: F401
 from .joints2feats import Joints2Feats                   # noqa: F401
+from .render import MotionRenderer, save_animation      # noqa: F401
 from .modules import LADiffDenoiser, LADiffVae          # noqa: F401
 from .pipeline import LADIFF, instantiate_from_config   # noqa: F401
 from .schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler    # noqa: F401
@@ -16,4 +17,4 @@ from .joint_metrics import ComputeMetrics, MRMetrics, TemosMetric   # noqa: F401
 from .losses import DiffusionLosses, MLDLosses   # noqa: F401
 
 __all__ = ["LADiffDenoiser", "LADiffVae", "LADIFF", "DDIMScheduler", "DDPMScheduler", "DPMSolverMultistepScheduler", "instantiate_from_config", "Feats2Joints", "MldTextEncoder", "MovementConvEncoder", "MotionEncoderBiGRUCo", "TextEncoderBiGRUCo",
-           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics", "validate", "MLDLosses", "DiffusionLosses"]
+           "TM2TMetrics", "MMMetrics", "evaluate", "get_metric_statistics", "ComputeMetrics", "TemosMetric", "MRMetrics", "validate", "MLDLosses", "DiffusionLosses", "MotionRenderer", "save_animation"]

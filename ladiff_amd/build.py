@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libladiff_hip.so")
-SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_kr.hip", "gemm_rowln.hip", "rowops.hip", "attention.hip", "qkv_attn.hip", "systolic.hip", "systolic_plan.hip", "linear_ca.hip", "dec_cross.hip", "dec_mlp.hip", "dec_post.hip", "dec_qkv_attn.hip", "feats2joints.hip", "joints2feats.hip", "joint_metrics.hip", "vae_losses.hip", "denoiser.hip", "diffusion_stage.hip", "decoder.hip", "encoder.hip", "clip.hip", "evaluator.hip", "reverse.hip", "api.hip"]
+SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_kr.hip", "gemm_rowln.hip", "rowops.hip", "attention.hip", "qkv_attn.hip", "systolic.hip", "systolic_plan.hip", "linear_ca.hip", "dec_cross.hip", "dec_mlp.hip", "dec_post.hip", "dec_qkv_attn.hip", "feats2joints.hip", "joints2feats.hip", "joint_metrics.hip", "render.hip", "vae_losses.hip", "denoiser.hip", "diffusion_stage.hip", "decoder.hip", "encoder.hip", "clip.hip", "evaluator.hip", "reverse.hip", "api.hip"]
 # -fvisibility=hidden: the library exports the C ABI of include/ladiff_hip.h (+ ladiff_hip_debug.h) and nothing else (LADIFF_API)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

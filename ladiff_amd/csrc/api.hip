@@ -792,6 +792,19 @@ int ladiff_joint_mr(const float* joints_rst, const float* joints_ref, const int3
     return launch_joint_mr(joints_rst, joints_ref, B, F, J, seq_rows, acc, S(stream));
 }
 
+// ------------------------------------------------------------------ motion renderer (csrc/render.hip)
+size_t ladiff_render_workspace_bytes(int B) { return render_ws_bytes(B); }
+
+int ladiff_render_motion(const float* joints, const int32_t* h_lengths, int B, int L, int njoints, const ladiff_render_params* params, int mode,
+                         int n_poses, int H, int W, void* out, int out_is_float, void* ws, size_t ws_bytes, ladiff_stream_t stream) {
+    if (njoints != 21 && njoints != 22) return LADIFF_ERR_UNSUPPORTED;      // the two skeletons whose chains the renderer restates
+    LADIFF_CHECK_ARG(B >= 0);
+    if (B == 0) return 0;
+    LADIFF_CHECK_ARG(joints && h_lengths && params && out && ws);
+    return launch_render_motion(joints, h_lengths, B, L, njoints, *params, mode, n_poses, H, W, out, out_is_float, (float*)ws, ws_bytes,
+                                S(stream));
+}
+
 // ------------------------------------------------------------------ LA-VAE decoder
 size_t ladiff_decoder_workspace_bytes(int B, int F, int T, int C) {
     (void)C;

@@ -123,6 +123,12 @@ int launch_feats2joints(const float* feats, const float* mean, const float* stdv
 int launch_joints2feats(const float* joints, const int32_t* h_lengths, int B, int L, const float* tgt, float feet_thre, const float* mean,
                         const float* stdv, float* feats, hipStream_t s);
 
+// render.hip: joints -> stick-figure images (the image model: include/ladiff_hip.h).  Every refusal but the NULL / B / njoints ones is
+// made here, on the host, before the first launch; ws holds render_ws_bytes(B) of per-motion scene records and nothing else
+size_t render_ws_bytes(int B);
+int launch_render_motion(const float* joints, const int32_t* h_lengths, int B, int L, int J, const ladiff_render_params& P, int mode,
+                         int n_poses, int H, int W, void* out, int out_is_float, float* ws, size_t ws_bytes, hipStream_t s);
+
 // joint_metrics.hip: one row of sums per sequence, then the rows added to acc in fp64 in sequence order
 int launch_joint_ape_ave(const float* rst, const float* ref, const int32_t* lengths, int B, int F, int J, const int32_t* part_idx,
                          float factor, float* seq_rows, double* acc, hipStream_t s);

@@ -29,6 +29,7 @@ from torch import nn
 from . import _lib
 from .feats2joints import Feats2Joints
 from .joints2feats import Joints2Feats
+from .render import MotionRenderer, save_animation
 from .schedulers import DDIMScheduler, DDPMScheduler, timestep_sinusoid
 
 _TARGET_ALIASES = {
@@ -136,6 +137,9 @@ class LADIFF(nn.Module):
         self.feats2joints_device = Feats2Joints.from_datamodule(datamodule) if datamodule is not None else None
         # the other direction (HumanML3D only): joints - `forward`'s own result, a mocap clip - to the features `edit` and `vae.encode` take
         self.joints2feats_device = Joints2Feats.from_datamodule(datamodule) if datamodule is not None else None
+        # joints to pictures (`render`, `strip`, `animate`, `preview(render="strip")`): built on first use for the datamodule's skeleton;
+        # assign a `MotionRenderer(njoints, size=..., **camera_and_style)` to change the pictures
+        self.renderer = None
         self.sample_mean = False
         self.fact = None
         self.times = []
@@ -835,12 +839,16 @@ class LADIFF(nn.Module):
                 out.append(feats.reshape(part.shape[0], B, feats.shape[1], feats.shape[2]))
         return out[0] if len(out) == 1 else torch.cat(out, dim=0)
 
-    def preview(self, batch, steps=None, kind="x0"):
+    def preview(self, batch, steps=None, kind="x0", render=None):
         """`forward` with the loop recorded: (joints, previews) - joints what `forward` returns, previews[k][b] the [L_b,22,3] joints of
         prompt b decoded from the `kind` ("x0": the step's data prediction, "latents": the latents after it) row of position steps[k]
-        (default: every position).  The film of a motion taking shape."""
+        (default: every position).  The film of a motion taking shape.  `render="strip"` makes it one that can be shown: the return
+        value becomes (joints, previews, pictures), pictures[b] a uint8 [S * H, W, 3] image on the host - the pose strips
+        (`LADIFF.strip`) of prompt b at the S chosen positions, stacked top to bottom."""
         if kind not in ("x0", "latents"):
             raise ValueError(f"kind {kind!r}: expected 'x0' or 'latents'")
+        if render not in (None, "strip"):
+            raise ValueError(f"render {render!r}: expected None or 'strip'")
         texts, lengths = batch["text"], [int(l) for l in batch["length"]]
         if self.text_encoder is None or (self.feats2joints is None and self.feats2joints_device is None):
             raise RuntimeError("LADIFF.preview needs a text_encoder callable and datamodule.feats2joints")
@@ -855,12 +863,64 @@ class LADIFF(nn.Module):
             frames = self.decode_trajectory(traj[kind], lengths, steps)
             S, B = int(frames.shape[0]), len(lengths)
             film = f2j(frames.reshape(S * B, frames.shape[2], frames.shape[3]).detach())
+            pictures = None
+            if render == "strip":                                        # sample k * B + b -> rows [k * H, (k + 1) * H) of picture b
+                strips = self.strip(film, lengths * S)
+                pictures = strips.reshape((S, B) + tuple(strips.shape[1:])).permute(1, 0, 2, 3, 4).reshape(B, S * strips.shape[1], *strips.shape[2:])
         torch.cuda.synchronize()
         self.check()
         self.times.append(time.time() - start)
         film = film.cpu()
         previews = [remove_padding(film[k * B:(k + 1) * B], lengths) for k in range(S)]
+        if pictures is not None:
+            return remove_padding(joints.cpu(), lengths), previews, list(pictures.cpu())
         return remove_padding(joints.cpu(), lengths), previews
+
+    def _render_input(self, joints, lengths):
+        """What `forward` returns - a list of [L_b,J,3] - or a padded [B,L,J,3] tensor with `lengths`, as (padded tensor on the model's
+        device, lengths)."""
+        if isinstance(joints, (list, tuple)):
+            if len(joints) == 0 or any(not torch.is_tensor(j) or j.dim() != 3 or j.shape[1:] != joints[0].shape[1:] for j in joints):
+                raise ValueError("joints as a list hold one [L_b, J, 3] tensor per motion")
+            if lengths is not None:
+                raise ValueError("a list of joints carries its lengths; give lengths with a padded tensor only")
+            lengths = [int(j.shape[0]) for j in joints]
+            padded = joints[0].new_zeros((len(joints), max(lengths)) + tuple(joints[0].shape[1:]))
+            for b, j in enumerate(joints):
+                padded[b, :lengths[b]] = j
+            joints = padded
+        elif not torch.is_tensor(joints):
+            raise TypeError("joints are a list of [L_b, J, 3] tensors or a padded [B, L, J, 3] tensor")
+        if self.renderer is None:
+            self.renderer = MotionRenderer(njoints=int(getattr(self.datamodule, "njoints", None) or joints.shape[-2]))
+        return joints.detach().to(self.device), lengths
+
+    def render(self, joints, lengths=None, **kw):
+        """Animation frames of motions, on the model's device: `MotionRenderer.__call__` (`self.renderer`) on what `forward` returned or
+        on a padded tensor with `lengths` -> [B, L', H, W, 3]; kw: dtype, frame_stride."""
+        joints, lengths = self._render_input(joints, lengths)
+        return self.renderer(joints, lengths, **kw)
+
+    def strip(self, joints, lengths=None, **kw):
+        """One pose strip per motion -> [B, H, W, 3] (`MotionRenderer.strip`); kw: n_poses, dtype."""
+        joints, lengths = self._render_input(joints, lengths)
+        return self.renderer.strip(joints, lengths, **kw)
+
+    def animate(self, batch, out_dir, fps=20, strip=True):
+        """`forward(batch)`, then per prompt i the files `<i>.gif` (the animation), `<i>.txt` (the prompt and the length, what demo.py
+        leaves beside its .npy) and, with `strip`, `<i>_strip.png` in `out_dir`.  Returns what `forward` returned.  The pictures are drawn
+        on the GPU; the copy to the host and the GIF encoding, which dominate the call, are not."""
+        joints = self.forward(batch)
+        frames = self.render(joints).cpu()
+        strips = self.strip(joints).cpu() if strip else None
+        os.makedirs(str(out_dir), exist_ok=True)
+        for i, j in enumerate(joints):
+            save_animation(frames[i, :j.shape[0]], os.path.join(str(out_dir), f"{i}.gif"), fps=fps)
+            with open(os.path.join(str(out_dir), f"{i}.txt"), "w") as f:
+                f.write(f"{batch['text'][i]}\n{int(j.shape[0])}\n")
+            if strips is not None:
+                save_animation(strips[i], os.path.join(str(out_dir), f"{i}_strip.png"))
+        return joints
 
     def forward(self, batch, latentwise_gen=None, plot_att_map=None):
         texts, lengths = batch["text"], batch["length"]
